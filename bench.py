@@ -6,6 +6,8 @@
 One "step" = one VecTask.step over this rank's environments = ONE launch of the fused step kernel (2 physics
 substeps + task logic).  Inputs (a pool of U(-1,1) action batches, seed 42) are resident in HBM before the timed
 region; the timed region holds exactly K steps between barrier+synchronize pairs; rank 0 prints one JSON line.
+`--dump-outputs DIR` writes what the headline leg's last timed step returned; that leg then times the steps that follow a
+fixed pre-roll from reset(), so that with the same arguments it computes the same thing in every run.
 """
 from __future__ import annotations
 
@@ -30,6 +32,10 @@ VALU_PEAK_TF = 157.3       # MI355X_MICROARCH.md: fp32 vector peak (packed v_pk_
 # wave at 1 / 2 / 4 waves per SIMD) -- half the packed peak.  Seconds per instruction per SIMD at two waves per SIMD:
 VALU_ISSUE_S_2W = 4.945e-3 / (20000 * 64 * 2)
 FLOPS_PER_ENV_STEP = 1.0e5 # useful flops of one env-step (2 substeps: ABA ~14 k + contact ~30 k each, task logic ~5 k), SURVEY 8(d)
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much
+# --dump-outputs: the dumped leg's W warm-up and K timed steps follow this many steps from reset() (~15 episodes of ~70 steps under
+# the random pool: the same mix of episode phases and in-kernel resets the other legs time; a multiple of the warm-up's chunks of 32)
+DUMP_PREROLL_STEPS = 1024
 
 
 def kernel_source_hash() -> str:
@@ -139,9 +145,31 @@ def _launch_ranks(args, argv) -> int:
     return 0
 
 
+def dump_outputs(directory, step_out):
+    """--dump-outputs: what the last timed step() returned to its caller -- observations, rewards, resets and the extras'
+    tensors -- as DIR/<name>.npy in float32.  Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of the environments (the
+    same rows of every array, listed in env_ids.npy) stands for the whole."""
+    import numpy as np
+    import torch
+    obs, rew, done, extras = step_out
+    arrays = {"obs": obs["obs"], "rew": rew, "done": done}
+    arrays.update({k: v for k, v in extras.items() if torch.is_tensor(v)})
+    arrays = {k: v.detach().to("cpu", torch.float32).numpy() for k, v in arrays.items()}
+    n = len(arrays["obs"])
+    row_bytes = sum(a.nbytes for a in arrays.values()) // n
+    if row_bytes * n > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // (row_bytes + 8), replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["env_ids"] = rows.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), v)
+
+
 class _PlumbingEnv:
     """--backend gloo: the N-rank plumbing of this script (launcher, env sharding, barriers, logging all-gather, MAX
-    reduction, JSON) on CPU tensors with a no-op step.  Its line is marked invalid; it exists for tests/test_bench_launcher.py."""
+    reduction, JSON, --dump-outputs) on CPU tensors with a no-op step.  Its line is marked invalid; it exists for
+    tests/test_bench_launcher.py."""
 
     def __init__(self, envs, rank):
         import torch
@@ -150,13 +178,28 @@ class _PlumbingEnv:
         abi.es_view(self._buf["env_state"], "episodes_finished")[:] = 1
         abi.es_view(self._buf["env_state"], "epi_len_log")[:] = float(rank + 1)
         self.episodes_finished = abi.es_view(self._buf["env_state"], "episodes_finished")
+        # step()'s return in the product's shapes: obs, done and stacked_rewards of env i hold i; rew and time_outs hold the index
+        # of the step that returned them (the step counter, which state_dict() carries as the real env's does)
+        ids = torch.arange(envs)
+        self._step_count = 0
+        self._out = ({"obs": ids.float()[:, None].expand(envs, abi.K["DW_NUM_OBS"]).contiguous()}, torch.zeros(envs), ids.clone(),
+                     {"time_outs": torch.zeros(envs, dtype=torch.int64), "stacked_rewards": ids.float()[:, None].expand(envs, 15).contiguous()})
+
+    def state_dict(self):
+        return dict({k: v.clone() for k, v in self._buf.items()}, _step_count=self._step_count)
 
     def reset(self):
         pass
 
     def step(self, a):
-        time.sleep(1e-3)
-        return None, None, None, None
+        # a 1 ms busy wait: a sleep overshoots by a varying amount (timer slack, wake-up latency), and the tests compare legs
+        t_end = time.perf_counter() + 1e-3
+        while time.perf_counter() < t_end:
+            pass
+        self._out[1].fill_(self._step_count)
+        self._out[3]["time_outs"].fill_(self._step_count)
+        self._step_count += 1
+        return self._out
 
     def close(self):
         pass
@@ -177,9 +220,14 @@ def main():
     ap.add_argument("--no-amp", action="store_true", help="skip the sibling-task leg (TocabiAMPLower, SURVEY 8 row f-3)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo = CPU plumbing rehearsal of the N-rank path (no kernel runs; the line is marked invalid)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the headline leg's last step returned (rank 0's envs) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         sys.exit(_launch_ranks(args, sys.argv[1:]))
@@ -212,10 +260,11 @@ def main():
         if not plumbing:
             torch.cuda.synchronize()
 
-    def run(envs, steps, warmup, alias_obs=False, mi=None, friction_dr=False, terrain=False, warm_seconds=None, fresh_actions=False):
+    def run(envs, steps, warmup, alias_obs=False, mi=None, friction_dr=False, terrain=False, warm_seconds=None, fresh_actions=False,
+            dump=None):
         """K steps of VecTask.step on `envs` envs of this rank.  alias_obs = False is the product's default contract (step() returns
         a fresh observation tensor, as the reference's torch.clamp does); True returns the view of obs_buf, so that the stream
-        holds nothing but the step kernel."""
+        holds nothing but the step kernel.  dump: directory for dump_outputs() of the last timed step."""
         if plumbing:
             env = _PlumbingEnv(envs, rank)
             pool = [torch.zeros(envs, 13)]
@@ -234,6 +283,13 @@ def main():
             g = torch.Generator(device=dev).manual_seed(42 + rank)
             pool = [torch.rand(envs, 13, generator=g, device=dev) * 2 - 1 for _ in range(64)]
         env.reset()
+        # The wall-time warm-up below runs a varying number of steps.  A dumped leg must compute the same thing in every run: the
+        # state after the warm-up's first DUMP_PREROLL_STEPS is copied aside (into memory taken here, before the warm-up) and put back
+        # after it, before the W warm-up steps -- device copies on the stream only (load_state_dict() syncs the host for its checks
+        # and, in the first leg, loads their kernels: the GPU then idles right before the timer).  Legs that are not dumped time the
+        # state the warm-up leaves.
+        start = env.state_dict() if dump else None
+        preroll = DUMP_PREROLL_STEPS if dump else 0
         # Warm by WALL TIME, then the W warm-up steps the caller asked for; the timed region is exactly K steps.  A driver run with
         # --warmup 5 --steps 20 is a 3 ms timed region that is the first GPU work of a fresh process: rounds 3 and 4 read it 8 % and
         # 12 % under the same run's 256-step leg, and a warm-up counted in steps (one logging horizon = 20 ms of GPU work) did not
@@ -249,15 +305,23 @@ def main():
         # not clocks or the synchronize, was what made the driver's --steps 20 line of rounds 3 and 4 read 8 - 12 % under its long leg.
         dwdist.gather_episode_stats(env._buf["env_state"])
         t_w, n_w = time.perf_counter(), 0
-        while n_w < HORIZON or time.perf_counter() - t_w < warm_seconds:
+        while n_w < max(HORIZON, preroll) or time.perf_counter() - t_w < warm_seconds:
             for i in range(32):
                 env.step(pool[(n_w + i) % len(pool)])
             n_w += 32
             sync()
+            if dump and n_w == preroll:
+                for k, v in env._buf.items():
+                    start[k].copy_(v)
+                start["_step_count"] = env._step_count
         if not plumbing:
             # (both events exist and have been recorded once before the timer starts: creating / first recording one loads code)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(); e1.record()
+        if dump:
+            for k, v in env._buf.items():
+                v.copy_(start[k])
+            env._step_count = start["_step_count"]
         if world > 1:
             dist.barrier()
         # The W warm-up steps come last, right before the synchronize that opens the timed region.
@@ -269,9 +333,9 @@ def main():
             e0.record()
         for i in range(steps):
             if fresh_actions:          # (SURVEY 8d's wording: the batch is regenerated on the device every step -- one torch kernel more on the stream)
-                env.step(torch.empty(envs, 13, device=dev).uniform_(-1.0, 1.0, generator=g))
+                last = env.step(torch.empty(envs, 13, device=dev).uniform_(-1.0, 1.0, generator=g))
             else:
-                env.step(pool[i % len(pool)])
+                last = env.step(pool[i % len(pool)])
             if (i + 1) % HORIZON == 0:
                 dwdist.gather_episode_stats(env._buf["env_state"])      # logging only, once per horizon
         if not plumbing:
@@ -280,6 +344,8 @@ def main():
         if world > 1:
             dist.barrier()
         wall = time.perf_counter() - t0
+        if dump:
+            dump_outputs(dump, last)
         # device time per step on the launch stream (HIP events on torch's current stream, which is the stream step() launches
         # on): the step's kernels, launch gaps included
         kernel_ms = (e0.elapsed_time(e1) / steps) if not plumbing else wall / steps * 1e3
@@ -310,7 +376,8 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    head = run(args.envs_per_gpu, args.steps, args.warmup)                 # the headline: the product's default obs contract
+    head = run(args.envs_per_gpu, args.steps, args.warmup,                 # the headline: the product's default obs contract
+               dump=args.dump_outputs if rank == 0 else None)
     wall_max = reduce_max(head["wall"])
     total_envs = args.envs_per_gpu * n_joined
     value = total_envs * args.steps / wall_max

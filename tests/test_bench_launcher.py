@@ -7,6 +7,12 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
+from bench import DUMP_PREROLL_STEPS
+from isaacgymdyros_amd import abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -54,11 +60,75 @@ def test_contradicting_world_size_is_an_error():
 def test_short_head_leg_reads_like_the_long_leg():
     """A driver-style short run (--steps well under 200) times a second, 256-step region in the same process; the two must
     tell the same ms/step (the 20-step headline read 12 % under its own long leg because the warm-up was
-    counted in steps).  On the plumbing env a step is a 1 ms sleep, so this checks the SHAPE of run(): warm by wall time,
-    events / gather exercised before the timer, exactly K steps inside it (5 % here: a sleep is a noisy clock; on the GPU the two legs
-    read within 2 %, gpurun_out/r5t_b.json)."""
+    counted in steps).  On the plumbing env a step is a 1 ms busy wait, so this checks the SHAPE of run(): warm by wall time,
+    events / gather exercised before the timer, exactly K steps inside it (5 % here: a host clock under other work is noisy; on the GPU
+    the two legs read within 2 %)."""
     p = _run(["--gpus", "1"], steps=100)
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads(p.stdout.strip().splitlines()[-1])
     assert out["steps"] == 100 and out["long_run"]["steps"] == 256
     assert abs(out["ms_per_step"] - out["long_run"]["ms_per_step"]) / out["long_run"]["ms_per_step"] < 0.05, (out["ms_per_step"], out["long_run"])
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the arrays the headline leg's last timed step returned, float32, one .npy per name.  On the plumbing env
+    obs / done / stacked_rewards of env i hold i and rew / time_outs the index of the step: the dumped leg restores the state of
+    step DUMP_PREROLL_STEPS after its wall-time warm-up, then runs max(W, 8) warm-up and K timed steps, whatever the warm-up ran."""
+    for d, steps, warm in (("a", 6, "0.01"), ("b", 11, "1.5")):
+        p = _run(["--gpus", "1", "--warm-seconds", warm, "--dump-outputs", str(tmp_path / d)], steps=steps)
+        assert p.returncode == 0, p.stderr[-2000:]
+        got = {f[:-4]: np.load(tmp_path / d / f) for f in os.listdir(tmp_path / d)}
+        assert set(got) == {"obs", "rew", "done", "time_outs", "stacked_rewards"}
+        assert got["obs"].shape == (16, abi.K["DW_NUM_OBS"]) and got["stacked_rewards"].shape == (16, 15)
+        ids = np.arange(16, dtype=np.float32)
+        last = DUMP_PREROLL_STEPS + 8 + steps - 1
+        for k, v in got.items():
+            assert v.dtype == np.float32 and len(v) == 16, k
+            want = np.full(16, last, np.float32) if k in ("rew", "time_outs") else ids
+            assert np.array_equal(v.reshape(16, -1), np.broadcast_to(want[:, None], v.reshape(16, -1).shape)), (k, v.ravel()[:4])
+
+
+def test_dump_outputs_samples_the_same_envs_above_64_mb(tmp_path):
+    """40000 envs of observations are 78 MB: a fixed seeded sample of envs (the same rows of every array, listed in env_ids)
+    keeps the dump under 64 MB, and two runs write the same files."""
+    dumps = []
+    for d in ("a", "b"):
+        p = _run(["--gpus", "1", "--envs-per-gpu", "40000", "--warm-seconds", "0.05", "--dump-outputs", str(tmp_path / d)], steps=2)
+        assert p.returncode == 0, p.stderr[-2000:]
+        dumps.append({f[:-4]: np.load(tmp_path / d / f) for f in os.listdir(tmp_path / d)})
+    a, b = dumps
+    assert set(a) == {"obs", "rew", "done", "time_outs", "stacked_rewards", "env_ids"}
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    rows = a["env_ids"]
+    assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 40000 and len(rows) > 30000
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+        if k in ("obs", "done", "stacked_rewards"):
+            assert a[k].dtype == np.float32 and np.array_equal(a[k].reshape(len(rows), -1)[:, 0], rows.astype(np.float32)), k
+    assert np.all(a["rew"] == DUMP_PREROLL_STEPS + 8 + 2 - 1)
+
+
+def test_steps_below_one_is_an_error():
+    p = _run(["--gpus", "1"], steps=0)
+    assert p.returncode != 0 and "--steps must be >= 1" in p.stderr
+
+
+@pytest.mark.gpu
+def test_dump_outputs_do_not_depend_on_the_warm_up(tmp_path):
+    """The wall-time warm-up runs a varying number of steps; the dumped leg's timed steps follow the state of step
+    DUMP_PREROLL_STEPS all the same, so two runs with the same arguments dump the same arrays bit for bit, here even with one
+    warm-up at the pre-roll's floor and one of 1 s."""
+    dumps = []
+    for d, warm in (("a", "0.01"), ("b", "1.0")):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "4",
+                            "--envs-per-gpu", "1024", "--warm-seconds", warm, "--no-cpu-baseline", "--no-also-4096", "--no-config5",
+                            "--no-terrain", "--no-ppo", "--no-amp", "--dump-outputs", str(tmp_path / d)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        dumps.append({f[:-4]: np.load(tmp_path / d / f) for f in os.listdir(tmp_path / d)})
+    a, b = dumps
+    assert set(a) == {"obs", "rew", "done", "time_outs", "stacked_rewards"}
+    assert a["obs"].shape == (1024, abi.K["DW_NUM_OBS"]) and np.isfinite(a["obs"]).all() and np.abs(a["obs"]).max() > 0
+    for k in a:
+        assert a[k].dtype == np.float32 and len(a[k]) == 1024, k
+        assert np.array_equal(a[k], b[k]), (k, np.abs(a[k] - b[k]).max())

@@ -85,11 +85,15 @@ def test_sigma_and_lr_schedules():
 
 
 def test_built_in_train_cfg_equals_the_reference_yaml():
-    path = "/root/reference/python/IsaacGymEnvs/isaacgymenvs/cfg/train/DyrosDynamicWalkPPO.yaml"
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present (GPU box)")
+    """Against the reference's train YAML as recorded in tests/golden/reference_cfg.json (oracle/make_live_goldens.py), and
+    against the YAML itself where the reference is mounted."""
+    import reference_cases as RC
+    with open(os.path.join(HERE, "golden", "reference_cfg.json")) as f:
+        ref = json.load(f)["train_yaml"]
+    if os.path.exists(RC.train_yaml_path()):
+        assert RC.train_yaml_record(RC.train_yaml_path()) == ref
     m = _mod()
-    ref = m.load_train_yaml(path)
+    assert ref["network"] and ref["config"]
     assert ref["network"] == m.TRAIN_CFG["network"]
     for k, v in ref["config"].items():
         assert m.TRAIN_CFG["config"][k] == v, (k, m.TRAIN_CFG["config"][k], v)

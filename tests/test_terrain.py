@@ -31,21 +31,18 @@ def test_matches_reference_samples(name, seed, ov):
 
 
 def test_live_against_reference_when_present():
+    """Live against the reference's Terrain where it is mounted; everywhere against its samples recorded in
+    tests/golden/reference_live.npz (oracle/make_live_goldens.py)."""
+    import reference_cases as RC
     from oracle import ref_harness
-    if not ref_harness.available():
-        pytest.skip("reference checkout not present (GPU box)")
-    ref_harness.load_reference(lambda: None)
-    ref_terrain, ref_cfg = sys.modules["isaacgymenvs.utils.terrain"], sys.modules["isaacgymenvs.cfg.terrain.terrain_cfg"]
-    ov = dict(mesh_type="heightfield", curriculum=False, num_rows=2, num_cols=5, border_size=1,
-              terrain_proportions=[0.1, 0.0, 0.2, 0.2, 0.2, 0.1, 0.1])
-    for seed in (0, 1, 2):
-        cfg = ref_cfg.TerrainCfg()
-        for k, v in ov.items():
-            setattr(cfg, k, v)
-        np.random.seed(seed)
-        r = ref_terrain.Terrain(cfg, 8)
-        m = Terrain(TerrainCfg(**ov), 8, seed=seed)
-        assert np.array_equal(m.heightsamples, r.heightsamples) and np.array_equal(m.env_origins, r.env_origins)
+    g = np.load(os.path.join(ROOT, "tests", "golden", "reference_live.npz"))
+    for seed in RC.TERRAIN_SEEDS:
+        m = Terrain(TerrainCfg(**RC.TERRAIN_LIVE), 8, seed=seed)
+        refs = [(g["terrain/%d/heightsamples" % seed], g["terrain/%d/env_origins" % seed])]
+        if ref_harness.available():
+            refs.append(RC.reference_terrain(seed))
+        for h, o in refs:
+            assert np.array_equal(m.heightsamples, h) and np.array_equal(m.env_origins, o)
 
 
 def test_plane_builds_nothing():

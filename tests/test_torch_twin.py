@@ -1,53 +1,42 @@
 """The eager-torch twin (oracle/torch_twin.py) against the reference's own functions (live, where the reference
 checkout is mounted) and against the committed goldens (everywhere)."""
+import os
+
 import numpy as np
-import pytest
 import torch
 
+import reference_cases as RC
 import replay as R
 from isaacgymdyros_amd import abi
 from oracle import ref_harness as RH
 from oracle import torch_twin as TW
 
 
-def _rand_inputs(N, model, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    r = lambda *s: torch.randn(*s, generator=g)
-    root = r(N, 13)
-    root[:, 3:7] = torch.nn.functional.normalize(r(N, 4) * 0.3 + torch.tensor([0, 0, 0, 1.0]), dim=1)
-    cf = torch.zeros(N, 38, 3)
-    cf[:, [model.left_foot_idx, model.right_foot_idx], 2] = torch.rand(N, 2, generator=g) * 1500
-    cf[::7, 3] = r(len(cf[::7]), 3) * 2
-    return dict(root=root, target_vel=torch.rand(N, 2, generator=g), tq=r(N, 33) * 0.3, tf=-torch.rand(N, 2, generator=g) * 600,
-                q=r(N, 33) * 0.3, qd=r(N, 33), pqd=r(N, 33), a=torch.rand(N, 13, generator=g) * 2 - 1,
-                ap=torch.rand(N, 13, generator=g) * 2 - 1, cf=cf, cfp=cf + r(N, 38, 3) * 20,
-                idx=torch.randint(0, 3599, (N, 1), generator=g), tm=100 + torch.rand(N, 1, generator=g) * 10)
-
-
-@pytest.mark.skipif(not RH.available(), reason="reference checkout not mounted")
 def test_twin_is_bitwise_the_reference_on_cpu(model, task_const):
-    from oracle.oracle import OracleSim
-    mods = RH.load_reference(lambda: None)
-    ref_reward = mods["task"].compute_humanoid_walk_reward
-    N = 512
-    d = _rand_inputs(N, model)
+    """Against the reference's functions' outputs recorded in tests/golden/reference_live.npz (oracle/make_live_goldens.py)
+    everywhere, and against the functions themselves where the reference is mounted."""
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_live.npz"))
+    refs = [{k: g[k] for k in g.files if k.startswith("twin/")}]
+    if RH.available():
+        refs.append(RC.reference_twin(model))
+    N = RC.TWIN_N
+    d = RC.twin_inputs(N, model)
     nf = model.non_feet_idxs()
-    crs = torch.zeros(N)
-    tot_ref, st_ref, names, crs_out = ref_reward(
-        torch.zeros(N, dtype=torch.long), torch.zeros(N, dtype=torch.long), d["target_vel"], d["root"], d["tq"], d["tf"], d["q"],
-        torch.zeros(N, 33), d["qd"], d["pqd"], d["a"], d["ap"], nf, d["cf"], d["cfp"], d["idx"], 0.6, 0.0, 1.0, d["tm"], crs,
-        model.right_foot_idx, model.left_foot_idx)
     tot, st, r8, qe, col = TW.reward(d["root"], d["target_vel"], d["tq"], d["tf"], d["q"], d["qd"], d["pqd"], d["a"], d["ap"], d["cf"],
                                      d["cfp"][:, model.left_foot_idx], d["cfp"][:, model.right_foot_idx], d["idx"], d["tm"], nf,
                                      model.left_foot_idx, model.right_foot_idx)
-    assert torch.equal(tot, tot_ref) and torch.equal(st, st_ref) and torch.equal(r8, crs_out)
-    assert len(names) == 14
     # quaternion helpers
-    qa = torch.nn.functional.normalize(torch.randn(N, 4), dim=1)
-    assert torch.equal(TW.quat_diff_rad(torch.tensor([[0, 0, 0, 1.0]]).expand(N, 4), qa),
-                       mods["jit_utils"].quat_diff_rad(torch.tensor([[0, 0, 0, 1.0]]).expand(N, 4).contiguous(), qa))
-    for a, b in zip(TW.quat2euler(qa), mods["torch_utils"].quat2euler(qa)):
-        assert torch.equal(a, b)
+    qa = RC.twin_quat_inputs()
+    qd = TW.quat_diff_rad(torch.tensor([[0, 0, 0, 1.0]]).expand(N, 4), qa)
+    eul = TW.quat2euler(qa)
+    for ref in refs:
+        assert torch.equal(tot, torch.from_numpy(ref["twin/total_reward"])) and torch.equal(st, torch.from_numpy(ref["twin/stacked_rewards"]))
+        assert torch.equal(r8, torch.from_numpy(ref["twin/crs"]))
+        assert int(ref["twin/num_reward_names"]) == 14
+        assert torch.equal(qd, torch.from_numpy(ref["twin/quat_diff_rad"]))
+        assert len(eul) == 3
+        for i, a in enumerate(eul):
+            assert torch.equal(a, torch.from_numpy(ref["twin/quat2euler_%d" % i]))
 
 
 def test_twin_reproduces_the_golden_observations_and_rewards(task_const, model):
