@@ -1,0 +1,186 @@
+#!/usr/bin/env python3
+"""The consumer side of TocabiAMPLower: the reference's AMP learner, restated in plain torch around the HIP discriminator
+(isaacgymdyros_amd/amp_disc.py).  Paths relative to python/IsaacGymEnvs/isaacgymenvs; configured by cfg/train/TocabiAMPLowerPPO.yaml
+(amp_disc.TRAIN_CFG, or --train_yaml):
+
+  network         separate actor / critic MLPs 512-512 relu (nn.Linear's own initialisation: initializer `default`), linear mu / value heads,
+                  a fixed log-sigma of sigma_init = -1.6 (`learn_sigma: False`).  sigma_last (-2.99) is NOT scheduled for this learner: the
+                  only code that reads it is learning/rl_games_custom/models_dyros.py:64-70 (the DYROS walk model); amp_continuous builds
+                  learning/amp_models.py's ModelAMPContinuous, whose sigma stays at its initial value.
+  play_steps      learning/amp_continuous.py:91-167 -- eval mode; next values zeroed on `terminate`; amp_obs recorded; the discriminator's
+                  reward over the whole rollout (ONE dwd_reward launch over horizon x envs rows), combined 0.7 task + 0.3 disc; GAE
+                  (common_agent.py:413-425)
+  train_epoch     :176-258 -- one demo top-up (512), a demo sample and a replay sample as large as the batch (the current batch on the first
+                  epoch), 6 mini epochs over minibatches of 131072 (or the whole batch if smaller), replay store with keep probability
+  calc_gradients  :260-329 -- clipped surrogate (e_clip 0.2), critic loss (critic_coef 5), bound loss (bounds_loss_coef 10, soft bound 1),
+                  the discriminator's share through AmpDiscriminator.update (its own Adam at the same learning rate: Adam is per parameter,
+                  so one optimiser over all parameters steps them alike; no clipping: truncate_grads False)
+  normalisation   normalize_input / normalize_value (rl_games' RunningMeanStd, amp_disc.RunningMeanStd), normalize_advantage over the batch
+  schedule        linear learning rate from 1e-4 to rl_games' LinearScheduler default minimum 1e-6 over max_epochs
+Prints step fps, total fps, the mean disc reward and the discriminator's logged values per epoch.
+"""
+from __future__ import annotations
+
+import argparse
+import math
+import os
+import sys
+import tempfile
+import time
+
+import torch
+import torch.nn as nn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from isaacgymdyros_amd import amp_disc as AD          # noqa: E402
+
+
+def mlp(n_in, units):
+    layers = []
+    for u in units:
+        layers += [nn.Linear(n_in, u), nn.ReLU()]
+        n_in = u
+    return nn.Sequential(*layers), n_in
+
+
+class ActorCritic(nn.Module):
+    def __init__(self, num_obs, num_act, units, sigma_init):
+        super().__init__()
+        self.actor_mlp, n = mlp(num_obs, units)
+        self.critic_mlp, _ = mlp(num_obs, units)
+        self.mu, self.value = nn.Linear(n, num_act), nn.Linear(n, 1)
+        self.sigma = nn.Parameter(torch.full((num_act,), float(sigma_init)), requires_grad=False)
+        self.obs_rms, self.value_rms = AD.RunningMeanStd(num_obs), AD.RunningMeanStd(1)
+
+    def forward(self, obs):
+        x = self.obs_rms(obs)
+        return self.mu(self.actor_mlp(x)), self.value(self.critic_mlp(x))
+
+    def neglogp(self, a, mu):
+        s = self.sigma
+        return 0.5 * (((a - mu) / torch.exp(s)) ** 2).sum(-1) + 0.5 * math.log(2 * math.pi) * a.shape[-1] + s.sum()
+
+    def unnorm_value(self, v):
+        r = self.value_rms
+        return v * torch.sqrt(r.running_var.float() + r.epsilon) + r.running_mean.float()
+
+
+def make_env(n, device, motion_file, synthetic):
+    from isaacgymdyros_amd.tocabi_amp_lower import TocabiAMPLower, default_amp_cfg
+    cfg = default_amp_cfg(n, device)
+    if synthetic:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import amp_motion_synth as SY
+        motion_file = SY.write(tempfile.mkdtemp(prefix="amp_synth_"))
+    if not motion_file:
+        raise SystemExit("give --motion_file (the task's motion yaml) or --synthetic")
+    cfg["env"]["motion_file"] = motion_file
+    return TocabiAMPLower(cfg, device, 0, True)
+
+
+def train(args):
+    tc = AD.load_train_yaml(args.train_yaml) if args.train_yaml else AD.TRAIN_CFG
+    c, netc = tc["config"], tc["network"]
+    dev = torch.device(args.device)
+    env = make_env(args.num_envs, args.device, args.motion_file, args.synthetic)
+    N, H, A = env.num_envs, int(c["horizon_length"]), env.num_actions
+    model = ActorCritic(env.num_obs, A, netc["mlp_units"], netc["sigma_init"]).to(dev)
+    lr0, lr_min, max_epochs = float(c["learning_rate"]), 1e-6, int(args.max_epochs or c["max_epochs"])
+    opt = torch.optim.Adam([p for p in model.parameters() if p.requires_grad], lr=lr0, eps=1e-8)
+    disc = AD.AmpDiscriminator(env.num_amp_obs, dev, tc, backend=args.backend)
+    disc.init_demo_buffer(env.fetch_amp_obs_demo)
+    gamma, tau, e_clip = float(c["gamma"]), float(c["tau"]), float(c["e_clip"])
+    mb = {"obs": torch.zeros(H, N, env.num_obs, device=dev), "act": torch.zeros(H, N, A, device=dev), "mu": torch.zeros(H, N, A, device=dev),
+          "nlp": torch.zeros(H, N, device=dev), "val": torch.zeros(H, N, 1, device=dev), "next_val": torch.zeros(H, N, 1, device=dev),
+          "rew": torch.zeros(H, N, 1, device=dev), "done": torch.zeros(H, N, device=dev), "amp": torch.zeros(H, N, env.num_amp_obs, device=dev)}
+    env.reset()
+    for epoch in range(args.epochs):
+        lr = lr_min + (lr0 - lr_min) * max(0, max_epochs - epoch) / max_epochs
+        for g in opt.param_groups:
+            g["lr"] = lr
+        t0 = time.time()
+        step_time = 0.0
+        model.eval()
+        with torch.no_grad():                                        # play_steps
+            for n in range(H):
+                obs = env.reset_done()[0]["obs"]
+                mu, v = model(obs)
+                act = mu + torch.exp(model.sigma) * torch.randn_like(mu)
+                mb["obs"][n], mb["act"][n], mb["mu"][n], mb["nlp"][n], mb["val"][n] = obs, act, mu, model.neglogp(act, mu), model.unnorm_value(v)
+                ts = time.time()
+                obs2, rew, done, infos = env.step(torch.clamp(act, -1.0, 1.0))
+                torch.cuda.synchronize(dev)
+                step_time += time.time() - ts
+                mb["rew"][n], mb["done"][n], mb["amp"][n] = rew.view(N, 1) * float(c["reward_scale"]), done.float(), infos["amp_obs"]
+                nv = model.unnorm_value(model(obs2["obs"])[1])
+                mb["next_val"][n] = nv * (1.0 - infos["terminate"].float().view(N, 1))
+            combined, disc_r = disc.rewards(mb["amp"], mb["rew"])     # _calc_amp_rewards + _combine_rewards
+            adv = torch.zeros_like(combined)
+            last = torch.zeros(N, 1, device=dev)
+            for t in reversed(range(H)):
+                delta = combined[t] + gamma * mb["next_val"][t] - mb["val"][t]
+                last = delta + gamma * tau * (1.0 - mb["done"][t]).view(N, 1) * last
+                adv[t] = last
+            ret = adv + mb["val"]
+        flat = lambda x: x.transpose(0, 1).reshape(N * H, *x.shape[2:])          # noqa: E731 (swap_and_flatten01)
+        obs_b, act_b, nlp_b, val_b, amp_b = (flat(mb[k]) for k in ("obs", "act", "nlp", "val", "amp"))
+        ret_b = flat(ret)
+        disc.update_demos(env.fetch_amp_obs_demo)
+        demo_b = disc.demo_buffer.sample(N * H)
+        replay_b = disc.replay_batch(amp_b)
+        with torch.no_grad():                                        # prepare_dataset: value normalisation, advantage normalisation
+            model.value_rms.train()
+            val_n, ret_n = model.value_rms(val_b), model.value_rms(ret_b)
+            model.value_rms.eval()
+            adv_b = ret_b - val_b
+            adv_b = (adv_b - adv_b.mean()) / (adv_b.std() + 1e-8)
+        model.train()
+        model.value_rms.eval()
+        B = min(int(c["minibatch_size"]), N * H)
+        amb = min(int(c["amp_minibatch_size"]), B)
+        losses = []
+        for _ in range(int(c["mini_epochs"])):
+            for i in range(0, N * H - B + 1, B):
+                s = slice(i, i + B)
+                mu, v = model(obs_b[s])
+                ratio = torch.exp(nlp_b[s] - model.neglogp(act_b[s], mu))
+                a = adv_b[s].view(-1)
+                a_loss = torch.max(-a * ratio, -a * torch.clamp(ratio, 1 - e_clip, 1 + e_clip)).mean()
+                c_loss = ((ret_n[s] - v) ** 2).mean()
+                b_loss = ((torch.clamp(mu - 1.0, min=0) ** 2 + torch.clamp(mu + 1.0, max=0) ** 2).sum(-1)).mean()
+                loss = a_loss + float(c["critic_coef"]) * c_loss + float(c["bounds_loss_coef"]) * b_loss
+                opt.zero_grad(set_to_none=True)
+                loss.backward()
+                opt.step()
+                disc.update(amp_b[s][:amb].contiguous(), replay_b[s][:amb].contiguous(), demo_b[s][:amb].contiguous(), lr=lr)
+                losses.append(torch.stack([a_loss.detach(), c_loss.detach(), b_loss.detach()]))
+        disc.store_replay(amp_b)
+        torch.cuda.synchronize(dev)
+        total = time.time() - t0
+        info = disc.pop_info()
+        al, cl, bl = torch.stack(losses).mean(0).tolist()
+        print("epoch %d  step fps %.0f  total fps %.0f  disc_r %.4f  a_loss %.4f  c_loss %.4f  b_loss %.4f  %s"
+              % (epoch, N * H / max(step_time, 1e-9), N * H / total, float(disc_r.mean()), al, cl, bl,
+                 "  ".join("%s %.4f" % (k.replace("disc_", ""), v) for k, v in info.items())), flush=True)
+        vals = [al, cl, bl, float(disc_r.mean()), float(combined.mean())] + list(info.values())
+        if not all(math.isfinite(x) for x in vals):
+            raise SystemExit("non-finite loss or reward at epoch %d" % epoch)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--num_envs", type=int, default=4096)
+    ap.add_argument("--epochs", type=int, default=10)
+    ap.add_argument("--max_epochs", type=int, default=0, help="of the learning-rate schedule (default: the yaml's)")
+    ap.add_argument("--motion_file", default=None)
+    ap.add_argument("--synthetic", action="store_true", help="the synthetic motion tables of tests/amp_motion_synth.py")
+    ap.add_argument("--train_yaml", default=None, help="cfg/train/TocabiAMPLowerPPO.yaml (default: the built-in copy of its values)")
+    ap.add_argument("--backend", default="hip", choices=["hip", "torch"])
+    ap.add_argument("--device", default="cuda:0")
+    train(ap.parse_args())
+
+
+if __name__ == "__main__":
+    main()
