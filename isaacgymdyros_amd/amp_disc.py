@@ -160,8 +160,9 @@ def torch_disc_loss(net: DiscNet, an, rn, dn, disc_coef, logit_reg, grad_penalty
     if weight_decay != 0:
         loss = loss + weight_decay * wd
     total = disc_coef * loss
-    return total, [total, pred, logit_loss, gp, wd, agent_logit.mean(), demo_logit.mean(), (agent_logit < 0).to(total.dtype).mean(),
-                   (demo_logit > 0).to(total.dtype).mean()]
+    # the accuracies as _compute_disc_acc takes them: means of fp32 flags whatever the module's dtype
+    return total, [total, pred, logit_loss, gp, wd, agent_logit.mean(), demo_logit.mean(), (agent_logit < 0).float().mean(),
+                   (demo_logit > 0).float().mean()]
 
 
 class ReplayBuffer:

@@ -37,7 +37,7 @@ def abs_logit64(d, xn):
     return h2 @ sd["_disc_logits.weight"].T.to(xn.device) + sd["_disc_logits.bias"].to(xn.device)
 
 
-@pytest.mark.parametrize("D", [34, 68, 102])
+@pytest.mark.parametrize("D", [34, 68, 102, 136, 340])
 @pytest.mark.parametrize("B", [1, 17, 4096, 131072])
 def test_reward_matches_torch(B, D):
     h, t = pair(D, seed=B + D)
@@ -114,6 +114,14 @@ def test_grad_terms_against_autograd(term):
 
 
 def test_grad_at_the_yaml_minibatch_shape():
+    """amp_minibatch_size 131 072 with numAMPObsSteps 2 (cfg/train/TocabiAMPLowerPPO.yaml): 3 x 131 072 rows at D = 68, 64 slabs.  (Against
+    float64: tests/test_amp_disc_reference_gpu.py.)"""
+    h, t = pair(68, seed=13)
+    rng = np.random.default_rng(14)
+    grads_agree(h, t, batch(rng, 131072, 68, -0.2), batch(rng, 131072, 68, 0.0), batch(rng, 131072, 68, 0.3))
+
+
+def test_grad_at_8192_rows_d102():
     h, t = pair(102, seed=5)
     rng = np.random.default_rng(6)
     grads_agree(h, t, batch(rng, 8192, 102, -0.2), batch(rng, 8192, 102, 0.0), batch(rng, 8192, 102, 0.3))
