@@ -18,6 +18,9 @@
   normalisation   normalize_input / normalize_value (rl_games' RunningMeanStd, amp_disc.RunningMeanStd), normalize_advantage over the batch
   schedule        linear learning rate from 1e-4 to rl_games' LinearScheduler default minimum 1e-6 over max_epochs
 Prints step fps, total fps, the mean disc reward and the discriminator's logged values per epoch.
+
+--policy_backend hip runs the actor-critic on isaacgymdyros_amd/amp_policy.py's AmpActorCritic instead (the rollout forward, the bootstrap
+values, GAE, the value normaliser and the minibatch updates on the dwa_ kernels); the default, torch, is the inline loop below.
 """
 from __future__ import annotations
 
@@ -35,6 +38,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from isaacgymdyros_amd import amp_disc as AD          # noqa: E402
+from isaacgymdyros_amd import amp_policy as AP        # noqa: E402
 
 
 def mlp(n_in, units):
@@ -86,8 +90,10 @@ def train(args):
     dev = torch.device(args.device)
     env = make_env(args.num_envs, args.device, args.motion_file, args.synthetic)
     N, H, A = env.num_envs, int(c["horizon_length"]), env.num_actions
-    model = ActorCritic(env.num_obs, A, netc["mlp_units"], netc["sigma_init"]).to(dev)
     lr0, lr_min, max_epochs = float(c["learning_rate"]), 1e-6, int(args.max_epochs or c["max_epochs"])
+    if args.policy_backend == "hip":
+        return train_hip(args, tc, dev, env, N, H, A, lr0, lr_min, max_epochs)
+    model = ActorCritic(env.num_obs, A, netc["mlp_units"], netc["sigma_init"]).to(dev)
     opt = torch.optim.Adam([p for p in model.parameters() if p.requires_grad], lr=lr0, eps=1e-8)
     disc = AD.AmpDiscriminator(env.num_amp_obs, dev, tc, backend=args.backend)
     disc.init_demo_buffer(env.fetch_amp_obs_demo)
@@ -169,6 +175,64 @@ def train(args):
             raise SystemExit("non-finite loss or reward at epoch %d" % epoch)
 
 
+def train_hip(args, tc, dev, env, N, H, A, lr0, lr_min, max_epochs):
+    """train() with the actor-critic on AmpActorCritic's kernels; the same epoch structure and the same printed line."""
+    c = tc["config"]
+    pol = AP.AmpActorCritic(env.num_obs, A, dev, tc, backend="hip")
+    disc = AD.AmpDiscriminator(env.num_amp_obs, dev, tc, backend=args.backend)
+    disc.init_demo_buffer(env.fetch_amp_obs_demo)
+    gamma, tau = float(c["gamma"]), float(c["tau"])
+    mb = {"obs": torch.zeros(H, N, env.num_obs, device=dev), "act": torch.zeros(H, N, A, device=dev), "nlp": torch.zeros(H, N, device=dev),
+          "val": torch.zeros(H, N, 1, device=dev), "next_val": torch.zeros(H, N, 1, device=dev), "rew": torch.zeros(H, N, 1, device=dev),
+          "done": torch.zeros(H, N, device=dev), "amp": torch.zeros(H, N, env.num_amp_obs, device=dev)}
+    env.reset()
+    for epoch in range(args.epochs):
+        lr = lr_min + (lr0 - lr_min) * max(0, max_epochs - epoch) / max_epochs
+        t0 = time.time()
+        step_time = 0.0
+        with torch.no_grad():                                        # play_steps
+            for n in range(H):
+                obs = env.reset_done()[0]["obs"].contiguous()
+                act, act_c, _mu, nlp, val = pol.act(obs, torch.randn(N, A, device=dev))
+                mb["obs"][n], mb["act"][n], mb["nlp"][n], mb["val"][n] = obs, act, nlp, val
+                ts = time.time()
+                obs2, rew, done, infos = env.step(act_c)
+                torch.cuda.synchronize(dev)
+                step_time += time.time() - ts
+                mb["rew"][n], mb["done"][n], mb["amp"][n] = rew.view(N, 1) * float(c["reward_scale"]), done.float(), infos["amp_obs"]
+                mb["next_val"][n] = pol.eval_critic(obs2["obs"].contiguous(), infos["terminate"].float().contiguous())
+            combined, disc_r = disc.rewards(mb["amp"], mb["rew"])     # _calc_amp_rewards + _combine_rewards
+            _adv, ret = AP.gae(mb["done"], mb["val"], combined, mb["next_val"], gamma, tau)
+        flat = lambda x: x.transpose(0, 1).reshape(N * H, *x.shape[2:])          # noqa: E731 (swap_and_flatten01)
+        obs_b, act_b, nlp_b, val_b, amp_b = (flat(mb[k]) for k in ("obs", "act", "nlp", "val", "amp"))
+        ret_b = flat(ret)
+        disc.update_demos(env.fetch_amp_obs_demo)
+        demo_b = disc.demo_buffer.sample(N * H)
+        replay_b = disc.replay_batch(amp_b)
+        with torch.no_grad():                                        # prepare_dataset: value normalisation, advantage normalisation
+            ret_n = pol.update_value_stats(val_b, ret_b).reshape(-1)
+            adv_b = ret_b - val_b
+            adv_b = ((adv_b - adv_b.mean()) / (adv_b.std() + 1e-8)).reshape(-1)
+        B = min(int(c["minibatch_size"]), N * H)
+        amb = min(int(c["amp_minibatch_size"]), B)
+        for _ in range(int(c["mini_epochs"])):
+            for i in range(0, N * H - B + 1, B):
+                s = slice(i, i + B)
+                pol.update(obs_b[s], act_b[s], nlp_b[s], adv_b[s], ret_n[s], lr=lr)
+                disc.update(amp_b[s][:amb].contiguous(), replay_b[s][:amb].contiguous(), demo_b[s][:amb].contiguous(), lr=lr)
+        disc.store_replay(amp_b)
+        torch.cuda.synchronize(dev)
+        total = time.time() - t0
+        info, pinfo = disc.pop_info(), pol.pop_info()
+        al, cl, bl = pinfo["a_loss"], pinfo["c_loss"], pinfo["b_loss"]
+        print("epoch %d  step fps %.0f  total fps %.0f  disc_r %.4f  a_loss %.4f  c_loss %.4f  b_loss %.4f  %s"
+              % (epoch, N * H / max(step_time, 1e-9), N * H / total, float(disc_r.mean()), al, cl, bl,
+                 "  ".join("%s %.4f" % (k.replace("disc_", ""), v) for k, v in info.items())), flush=True)
+        vals = [al, cl, bl, float(disc_r.mean()), float(combined.mean())] + list(info.values())
+        if not all(math.isfinite(x) for x in vals):
+            raise SystemExit("non-finite loss or reward at epoch %d" % epoch)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--num_envs", type=int, default=4096)
@@ -178,6 +242,7 @@ def main():
     ap.add_argument("--synthetic", action="store_true", help="the synthetic motion tables of tests/amp_motion_synth.py")
     ap.add_argument("--train_yaml", default=None, help="cfg/train/TocabiAMPLowerPPO.yaml (default: the built-in copy of its values)")
     ap.add_argument("--backend", default="hip", choices=["hip", "torch"])
+    ap.add_argument("--policy_backend", default="torch", choices=["torch", "hip"], help="the actor-critic: the inline torch loop or AmpActorCritic")
     ap.add_argument("--device", default="cuda:0")
     train(ap.parse_args())
 

@@ -21,7 +21,7 @@ KERNEL_UNIT = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp", "-mllvm", "-amd
 SOURCES = [("dw_hip.hip", []),
            ("dw_oct_kernels.hip", KERNEL_UNIT),
            ("dw_hex_kernels.hip", KERNEL_UNIT), ("dw_amp.hip", []), ("dw_ppo.hip", ["-munsafe-fp-atomics"]),
-           ("dw_amp_disc.hip", [])]
+           ("dw_amp_disc.hip", []), ("dw_amp_policy.hip", ["-ffp-contract=off"])]
 HEADERS = ["dw_wave.h", "dw_devmodel.h", "dw_physics.h", "dw_task.h", "dw_params.h", "dw_quad_wave.h", "dw_quad_model.h",
            "dw_limb.h", "dw_bufg.h", "dw_oct.h", "dw_oct_kernels.h", "dw_oct_post.h", "dw_handle.h", "dw_amp.h", "dw_amp_step.h"]
 # -fno-slp-vectorize: the SLP vectoriser packs adjacent scalar f32 math into v_pk_*_f32 pairs: in the octet step kernel 1 920
@@ -43,7 +43,8 @@ def stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in [s for s, _ in SOURCES] + HEADERS] + [os.path.join(os.path.dirname(PKG), "include", h) for h in ("dyros_walk.h", "dyros_ppo.h", "dyros_amp_disc.h")]
+    deps = [os.path.join(CSRC, f) for f in [s for s, _ in SOURCES] + HEADERS] + [os.path.join(os.path.dirname(PKG), "include", h) for h in ("dyros_walk.h", "dyros_ppo.h", "dyros_amp_disc.h",
+                                                                                                                                  "dyros_amp_policy.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
