@@ -19,6 +19,11 @@
   schedule        linear learning rate from 1e-4 to rl_games' LinearScheduler default minimum 1e-6 over max_epochs
 Prints step fps, total fps, the mean disc reward and the discriminator's logged values per epoch.
 
+Checkpoints (isaacgymdyros_amd/amp_checkpoint.py, the reference learner's layout; common_agent.py:65-67, 124, 172-178): with --output_dir,
+<output_dir>/<name>/nn/<name>_<epoch>.pth every --save_frequency completed epochs and <name>.pth at the end (<name>: TocabiAMPLower).  With
+--checkpoint the run resumes from such a file: weights, normalisers, both Adam states, the AMP buffers and the learning-rate schedule; the
+epoch numbering continues and --epochs more epochs run.
+
 --policy_backend hip runs the actor-critic on isaacgymdyros_amd/amp_policy.py's AmpActorCritic instead (the rollout forward, the bootstrap
 values, GAE, the value normaliser and the minibatch updates on the dwa_ kernels); the default, torch, is the inline loop below.
 """
@@ -37,6 +42,7 @@ import torch.nn as nn
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from isaacgymdyros_amd import amp_checkpoint as CK    # noqa: E402
 from isaacgymdyros_amd import amp_disc as AD          # noqa: E402
 from isaacgymdyros_amd import amp_policy as AP        # noqa: E402
 
@@ -84,6 +90,49 @@ def make_env(n, device, motion_file, synthetic):
     return TocabiAMPLower(cfg, device, 0, True)
 
 
+class Checkpoints:
+    """--checkpoint / --output_dir / --save_frequency for one run: resume() before the first epoch, after_epoch() after each, finish() at the end."""
+
+    def __init__(self, args, N, H, lr0, lr_min, max_epochs):
+        self.args, self.rows = args, N * H
+        self.sched = {"lr0": lr0, "lr_min": lr_min, "max_epochs": max_epochs}
+        self.dir = os.path.join(args.output_dir, CK.NAME, "nn") if args.output_dir else None
+        self.freq = args.save_frequency
+        if self.freq is None:
+            self.freq = CK.SAVE_FREQUENCY
+            if args.train_yaml:
+                import yaml
+                self.freq = int(yaml.safe_load(open(args.train_yaml))["params"]["config"].get("save_frequency", CK.SAVE_FREQUENCY))
+
+    def resume(self, policy, disc) -> int:
+        """The first epoch of this run (0, or the checkpoint's completed epochs); the schedule continues with the checkpoint's values."""
+        if not self.args.checkpoint:
+            return 0
+        c = CK.restore(self.args.checkpoint, policy, disc)
+        for k in self.sched:
+            if c[k] is not None:
+                self.sched[k] = c[k]
+        print("resumed %s at epoch %d" % (self.args.checkpoint, c["epoch"]), flush=True)
+        return c["epoch"]
+
+    def lr(self, epoch):
+        s = self.sched
+        return s["lr_min"] + (s["lr0"] - s["lr_min"]) * max(0, s["max_epochs"] - epoch) / s["max_epochs"]
+
+    def _save(self, name, policy, disc, done):
+        path = CK.save(os.path.join(self.dir, name + ".pth"), policy, disc, done, done * self.rows, **self.sched)
+        print("saved %s epoch %d lr %.9e" % (path, done, policy.optimizer_state()["lr"]), flush=True)
+
+    def after_epoch(self, epoch, policy, disc):
+        done = epoch + 1
+        if self.dir and self.freq > 0 and done % self.freq == 0:
+            self._save("%s_%d" % (CK.NAME, done), policy, disc, done)
+
+    def finish(self, epoch_end, policy, disc):
+        if self.dir:
+            self._save(CK.NAME, policy, disc, epoch_end)
+
+
 def train(args):
     tc = AD.load_train_yaml(args.train_yaml) if args.train_yaml else AD.TRAIN_CFG
     c, netc = tc["config"], tc["network"]
@@ -101,9 +150,11 @@ def train(args):
     mb = {"obs": torch.zeros(H, N, env.num_obs, device=dev), "act": torch.zeros(H, N, A, device=dev), "mu": torch.zeros(H, N, A, device=dev),
           "nlp": torch.zeros(H, N, device=dev), "val": torch.zeros(H, N, 1, device=dev), "next_val": torch.zeros(H, N, 1, device=dev),
           "rew": torch.zeros(H, N, 1, device=dev), "done": torch.zeros(H, N, device=dev), "amp": torch.zeros(H, N, env.num_amp_obs, device=dev)}
+    ckp, learner = Checkpoints(args, N, H, lr0, lr_min, max_epochs), CK.TorchLearner(model, opt)
+    first = ckp.resume(learner, disc)
     env.reset()
-    for epoch in range(args.epochs):
-        lr = lr_min + (lr0 - lr_min) * max(0, max_epochs - epoch) / max_epochs
+    for epoch in range(first, first + args.epochs):
+        lr = ckp.lr(epoch)
         for g in opt.param_groups:
             g["lr"] = lr
         t0 = time.time()
@@ -173,6 +224,8 @@ def train(args):
         vals = [al, cl, bl, float(disc_r.mean()), float(combined.mean())] + list(info.values())
         if not all(math.isfinite(x) for x in vals):
             raise SystemExit("non-finite loss or reward at epoch %d" % epoch)
+        ckp.after_epoch(epoch, learner, disc)
+    ckp.finish(first + args.epochs, learner, disc)
 
 
 def train_hip(args, tc, dev, env, N, H, A, lr0, lr_min, max_epochs):
@@ -185,9 +238,11 @@ def train_hip(args, tc, dev, env, N, H, A, lr0, lr_min, max_epochs):
     mb = {"obs": torch.zeros(H, N, env.num_obs, device=dev), "act": torch.zeros(H, N, A, device=dev), "nlp": torch.zeros(H, N, device=dev),
           "val": torch.zeros(H, N, 1, device=dev), "next_val": torch.zeros(H, N, 1, device=dev), "rew": torch.zeros(H, N, 1, device=dev),
           "done": torch.zeros(H, N, device=dev), "amp": torch.zeros(H, N, env.num_amp_obs, device=dev)}
+    ckp = Checkpoints(args, N, H, lr0, lr_min, max_epochs)
+    first = ckp.resume(pol, disc)
     env.reset()
-    for epoch in range(args.epochs):
-        lr = lr_min + (lr0 - lr_min) * max(0, max_epochs - epoch) / max_epochs
+    for epoch in range(first, first + args.epochs):
+        lr = ckp.lr(epoch)
         t0 = time.time()
         step_time = 0.0
         with torch.no_grad():                                        # play_steps
@@ -231,6 +286,8 @@ def train_hip(args, tc, dev, env, N, H, A, lr0, lr_min, max_epochs):
         vals = [al, cl, bl, float(disc_r.mean()), float(combined.mean())] + list(info.values())
         if not all(math.isfinite(x) for x in vals):
             raise SystemExit("non-finite loss or reward at epoch %d" % epoch)
+        ckp.after_epoch(epoch, pol, disc)
+    ckp.finish(first + args.epochs, pol, disc)
 
 
 def main():
@@ -244,6 +301,9 @@ def main():
     ap.add_argument("--backend", default="hip", choices=["hip", "torch"])
     ap.add_argument("--policy_backend", default="torch", choices=["torch", "hip"], help="the actor-critic: the inline torch loop or AmpActorCritic")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--output_dir", default=None, help="write checkpoints under <output_dir>/TocabiAMPLower/nn (default: none are written)")
+    ap.add_argument("--save_frequency", type=int, default=None, help="a checkpoint every this many epochs (default: the yaml's, 100)")
+    ap.add_argument("--checkpoint", default=None, help="resume from this checkpoint")
     train(ap.parse_args())
 
 

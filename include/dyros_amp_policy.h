@@ -9,6 +9,8 @@
  *               critic loss, soft bound loss, backward to every parameter
  *   dwa_opt     the optimiser step (torch.optim.Adam, betas 0.9 / 0.999, eps 1e-8, no weight decay, no clipping), then g = 0
  *   dwa_gae     common_agent.discount_values with mb_next_values, the same fp32 operations in the same order per element
+ *   dwa_play    the player's get_action in eval mode (learning/common_player.py, amp_players.py): the actor only, deterministic or sampled,
+ *               clamped to the +-1 action space
  * The nets: x [D] -> relu(W1 x + b1) [512] -> relu(W2 h1 + b2) [512] -> mu [A] (actor) / value [1] (critic); fp32 throughout, the
  * products on the matrix cores (v_mfma_f32_16x16x4_f32).  All pointers are device pointers; every function enqueues on `stream` and
  * returns 0, or -1 with dwa_last_error() set.  No function allocates, synchronises with the host or reads anything but its arguments, so
@@ -28,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DWA_ABI_VERSION 1
+#define DWA_ABI_VERSION 2
 #define DWA_HID       512   /* cfg/train/TocabiAMPLowerPPO.yaml network.mlp.units [512, 512]: the only width accepted */
 #define DWA_D_MAX     512
 #define DWA_A_MAX     16
@@ -87,6 +89,16 @@ int dwa_opt(float *p, float *g, float *m, float *v, float *state, int32_t D, int
  * gamma_tau is the product gamma * tau as the reference forms it (in double, then used as an fp32 scalar). */
 int dwa_gae(const float *done, const float *values, const float *rewards, const float *next_values, int32_t H, int32_t N, float gamma,
             float gamma_tau, float *adv, float *ret, void *stream);
+
+/* Bytes of device workspace dwa_play needs for N rows (0: none, work may be NULL); -1 for bad arguments. */
+int64_t dwa_play_workspace_bytes(int32_t N, int32_t D, int32_t A);
+
+/* Play-time policy over N rows, the actor only: x = clamp((obs - mean) / sqrt(var + 1e-5), -5, 5) with obs_stats (eval mode: they stay),
+ * mu [N][A] = W3 relu(W2 relu(W1 x + b1) + b2) + b3; clamped [N][A] = clamp(mu, -1, 1) with noise == NULL (the deterministic player), else
+ * clamp(mu + exp(logstd) noise, -1, 1) with noise [N][A] standard normal draws (logstd may be NULL without noise).  mu may be NULL.
+ * N <= 64 runs three launches of column slices (work: dwa_play_workspace_bytes), larger N one launch of 16-row workgroups. */
+int dwa_play(const float *p, const double *obs_stats, const float *logstd, const float *obs, const float *noise, int32_t N, int32_t D, int32_t A,
+             float *clamped, float *mu, void *work, int64_t work_bytes, void *stream);
 
 #ifdef __cplusplus
 }

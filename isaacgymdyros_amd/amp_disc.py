@@ -453,3 +453,24 @@ class AmpDiscriminator:
                 v.copy_(sd[k])
             for k, v in self.rms.state_dict().items():
                 v.copy_(sd["_amp_input_mean_std." + k])
+
+    def optimizer_state(self) -> dict:
+        """The Adam state in amp_policy's backend-neutral form ({"lr", "step", "exp_avg", "exp_avg_sq"} by parameter name): hip: m, v and the
+        DWD_S_LR / DWD_S_STEP words; torch: torch.optim.Adam's state."""
+        from .amp_policy import _adam_state
+        return _adam_state(self.backend, getattr(self, "opt", None), self._named_params(), self.m, self.v, self.state, K["DWD_S_LR"],
+                           K["DWD_S_STEP"])
+
+    def load_optimizer_state(self, st: dict):
+        """optimizer_state()'s dict, written by either backend."""
+        from .amp_policy import _load_adam_state
+        _load_adam_state(self.backend, getattr(self, "opt", None), self._named_params(), self.m, self.v, self.state, K["DWD_S_LR"],
+                         K["DWD_S_STEP"], st)
+
+    def _named_params(self):
+        names = {id(t): n for n, t in self.net.named_parameters()}
+        out, o = [], 0
+        for t in self._params_in_layout():
+            out.append((names[id(t)], t, o))
+            o += t.numel()
+        return out

@@ -11,7 +11,7 @@ Reference (python/IsaacGymEnvs/isaacgymenvs/): learning/amp_continuous.py and le
   * calc_gradients (:260-329): the clipped surrogate (e_clip 0.2), the critic loss (critic_coef 5, clip_value False), the soft bound loss
     (bounds_loss_coef 10), no entropy term (entropy_coef 0), Adam (eps 1e-8) without clipping (truncate_grads False).
 
-Two backends of one class: `backend="hip"` (the product: dwa_stats, dwa_act, dwa_critic, dwa_grad, dwa_opt, dwa_gae) and `backend="torch"`
+Two backends of one class: `backend="hip"` (the product: dwa_stats, dwa_act, dwa_critic, dwa_grad, dwa_opt, dwa_gae, dwa_play) and `backend="torch"`
 (the arithmetic of examples/amp_consumer.py's inline loop: the yardstick of the tests and the CPU form).  Parameter names are those of the
 consumer's ActorCritic, so a state_dict of either backend loads into the other.
 """
@@ -38,7 +38,8 @@ def _constants() -> dict:
 
 K = _constants()
 HID, D_MAX, A_MAX = K["DWA_HID"], K["DWA_D_MAX"], K["DWA_A_MAX"]
-EXPORTS = ["abi_version", "last_error", "workspace_bytes", "stats_workspace_bytes", "stats", "act", "critic", "grad", "opt", "gae"]
+EXPORTS = ["abi_version", "last_error", "workspace_bytes", "stats_workspace_bytes", "stats", "act", "critic", "grad", "opt", "gae",
+           "play_workspace_bytes", "play"]
 LOG_NAMES = ["a_loss", "c_loss", "b_loss", "clip_frac"]
 
 
@@ -119,7 +120,9 @@ def declare(lib: C.CDLL) -> dict:
            "critic": fn("critic", C.c_int, P, P, P, P, P, I32, I32, I32, P, P, I64, P),
            "grad": fn("grad", C.c_int, P, P, P, P, P, P, P, P, I32, I32, I32, DwaLoss, P, P, P, I64, P),
            "opt": fn("opt", C.c_int, P, P, P, P, P, I32, I32, P),
-           "gae": fn("gae", C.c_int, P, P, P, P, I32, I32, F, F, P, P, P)}
+           "gae": fn("gae", C.c_int, P, P, P, P, I32, I32, F, F, P, P, P),
+           "play_workspace_bytes": fn("play_workspace_bytes", I64, I32, I32, I32),
+           "play": fn("play", C.c_int, P, P, P, P, P, I32, I32, I32, P, P, P, I64, P)}
     if api["abi_version"]() != K["DWA_ABI_VERSION"]:
         raise RuntimeError("libdyroswalk_hip.so: dwa ABI %d, include/dyros_amp_policy.h %d: rebuild" % (api["abi_version"](), K["DWA_ABI_VERSION"]))
     return api
@@ -269,6 +272,31 @@ class AmpActorCritic:
                                w, nb, self._stream()))
         return a, ac, mu, nlp, val
 
+    def play(self, obs, noise=None):
+        """The player's get_action (eval mode, the actor only): (clamped [N, A], mu [N, A]).  noise None: clamped = clamp(mu, -1, 1), the
+        deterministic player; else [N, A] standard-normal draws: clamped = clamp(mu + exp(sigma) noise, -1, 1).  No statistic moves."""
+        N = self._rows("obs", obs, self.D)
+        if noise is not None:
+            _req("noise", noise, torch.float32, self.device, (N, self.A))
+        if self.backend == "torch":
+            with torch.no_grad():
+                self.net.eval()
+                mu = self.net.mu(self.net.actor_mlp(self.net.obs_rms(obs)))
+                a = mu if noise is None else mu + torch.exp(self.net.sigma) * noise
+                return torch.clamp(a, -1.0, 1.0), mu
+        clamped, mu = torch.empty(N, self.A, device=self.device), torch.empty(N, self.A, device=self.device)
+        key = ("play", N)
+        if key not in self._work:
+            nb = self.api["play_workspace_bytes"](N, self.D, self.A)
+            if nb < 0:
+                raise ValueError("dwa_play: %d rows" % N)
+            self._work[key] = torch.empty(max(nb, 4) // 4, dtype=torch.float32, device=self.device)
+        w = self._work[key]
+        _check(self.api["play"](self.p.data_ptr(), self.obs_stats.data_ptr(), self.net.sigma.data_ptr(), obs.data_ptr(),
+                                None if noise is None else noise.data_ptr(), N, self.D, self.A, clamped.data_ptr(), mu.data_ptr(), w.data_ptr(),
+                                w.numel() * 4, self._stream()))
+        return clamped, mu
+
     def eval_critic(self, obs, terminate):
         """_eval_critic for the bootstrap: the unnormalised value [N, 1] times (1 - terminate [N])."""
         N = self._rows("obs", obs, self.D)
@@ -404,3 +432,57 @@ class AmpActorCritic:
         with torch.no_grad():
             for k, v in self.net.state_dict().items():
                 v.copy_(sd[k])
+
+    def optimizer_state(self) -> dict:
+        """The Adam state in a backend-neutral form: {"lr", "step", "exp_avg": {name: tensor}, "exp_avg_sq": {name: tensor}} over the trained
+        parameters (state_dict names, sigma excluded).  hip: m, v and the DWA_S_LR / DWA_S_STEP words; torch: torch.optim.Adam's state."""
+        return _adam_state(self.backend, getattr(self, "opt", None), self._named_params(), self.m, self.v, self.state, K["DWA_S_LR"], K["DWA_S_STEP"])
+
+    def load_optimizer_state(self, st: dict):
+        """optimizer_state()'s dict, written by either backend."""
+        _load_adam_state(self.backend, getattr(self, "opt", None), self._named_params(), self.m, self.v, self.state, K["DWA_S_LR"], K["DWA_S_STEP"], st)
+
+    def _named_params(self):
+        """(name, parameter, offset into p) of the trained parameters in the layout order."""
+        names = {id(t): n for n, t in self.net.named_parameters()}
+        out, o = [], 0
+        for t in self.net.params_in_layout():
+            out.append((names[id(t)], t, o))
+            o += t.numel()
+        return out
+
+
+def _adam_state(backend, opt, named, m, v, state, i_lr, i_step) -> dict:
+    """optimizer_state() of a learner: named = [(name, parameter, offset into the flat m / v)]."""
+    if backend == "torch":
+        lr = float(opt.param_groups[0]["lr"])
+        step = 0
+        ea, es = {}, {}
+        for n, t, _o in named:
+            s = opt.state.get(t, {})
+            step = max(step, int(float(s["step"]))) if "step" in s else step
+            ea[n] = s["exp_avg"].detach().clone() if "exp_avg" in s else torch.zeros_like(t.detach())
+            es[n] = s["exp_avg_sq"].detach().clone() if "exp_avg_sq" in s else torch.zeros_like(t.detach())
+        return {"lr": lr, "step": step, "exp_avg": ea, "exp_avg_sq": es}
+    sv = state.cpu()
+    return {"lr": float(sv[i_lr]), "step": int(sv[i_step]),
+            "exp_avg": {n: m[o:o + t.numel()].view_as(t).clone() for n, t, o in named},
+            "exp_avg_sq": {n: v[o:o + t.numel()].view_as(t).clone() for n, t, o in named}}
+
+
+def _load_adam_state(backend, opt, named, m, v, state, i_lr, i_step, st: dict):
+    step, lr = int(st["step"]), float(st["lr"])
+    with torch.no_grad():
+        state[i_lr], state[i_step] = lr, float(step)
+        if backend == "torch":
+            for pg in opt.param_groups:
+                pg["lr"] = lr
+            opt.state.clear()
+            if step > 0:
+                for n, t, _o in named:
+                    opt.state[t] = {"step": torch.tensor(float(step)), "exp_avg": st["exp_avg"][n].to(t.device, torch.float32).clone(),
+                                    "exp_avg_sq": st["exp_avg_sq"][n].to(t.device, torch.float32).clone()}
+            return
+        for n, t, o in named:
+            m[o:o + t.numel()].copy_(st["exp_avg"][n].reshape(-1))
+            v[o:o + t.numel()].copy_(st["exp_avg_sq"][n].reshape(-1))

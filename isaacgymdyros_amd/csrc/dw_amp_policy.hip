@@ -444,6 +444,187 @@ __global__ __launch_bounds__(256) void dwa_gae_scan(const float *__restrict__ do
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------- play
+// dwa_play: the actor alone, eval mode.  Every product is v_mfma_f32_16x16x4_f32 on one 16-row tile; the k index of a
+// 16-deep block is permuted so that lane (li, lk) feeds k = 4 lk + kk to the kk-th MFMA of the block: its A and W words are then four
+// consecutive floats (one ds_read_b128 / global_load_dwordx4 each), and W's rows are read in 64-byte pieces.  Two forms:
+//   N > PLAY_SMALL_N  dwa_play_rows: one launch of 16-row workgroups; the normalised rows and both hidden layers stay in LDS (2 x 16 x 516
+//                     floats, two workgroups per CU), each wave makes 128 of the 512 columns of a layer, the actor's weights stream from L2
+//   N <= PLAY_SMALL_N dwa_play_cols (x 2) and dwa_play_head: a 16-column slice of a layer per workgroup (32 workgroups share the weights
+//                     instead of each reading all 2 MB), its four waves split K, the quarters added in wave order; h1 and h2 go through the
+//                     workspace
+// Both end in play_out: the mu head as one 16 x 16 tile whose K the four waves split, added in wave order, then the bias, the optional noise
+// and the clamp.  No atomics: a replay gives the bits of the eager call.
+constexpr int PR = 16;                  // rows per workgroup of dwa_play_rows / dwa_play_head
+constexpr int PS = HID + 4;             // LDS row length (floats) of their row images: >= any D rounded up to 16
+constexpr int PLAY_SMALL_N = 64;        // the largest N of the column-split form (four row tiles per wave)
+static_assert(DWA_D_MAX <= HID, "the input rows share the hidden-layer row images");
+
+struct Play {
+    const float *p, *logstd, *obs, *noise;
+    const double *st;
+    float *clamped, *mu, *h1, *h2;
+    int N, D, A, pal, oal;              // pal / oal: p / obs 16-byte aligned (and D a multiple of 4) -- the vector loads are allowed
+};
+
+// four consecutive floats of a row from k; zeros from kmax on (vec: the row is 16-byte aligned wherever k is)
+__device__ __forceinline__ f4 ld4(const float *__restrict__ row, int k, int kmax, int vec) {
+    if (vec && k + 4 <= kmax) return *(const f4 *)(row + k);
+    f4 x;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) x[q] = k + q < kmax ? row[k + q] : 0.0f;
+    return x;
+}
+
+// acc[j] += A [16 rows of lda floats, LDS] x W[c0 + 16 j + li][k]^T over k < kpad (a multiple of 16), W read as zero from K or column ncol on
+template <int NT>
+__device__ __forceinline__ void play_mm(const float *As, int lda, const float *__restrict__ W, int ldw, int K, int kpad, int c0, int ncol, int lane,
+                                        int vec, f4 (&acc)[NT]) {
+    const int li = lane & 15, lk = lane >> 4;
+    f4 b[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int c = c0 + 16 * j + li;
+        b[j] = c < ncol ? ld4(W + (size_t)c * ldw, 4 * lk, K, vec) : (f4){0.0f, 0.0f, 0.0f, 0.0f};
+    }
+    for (int kb = 0; kb < kpad; kb += 16) {
+        f4 bn[NT];
+        if (kb + 16 < kpad) {          // (the next block's weights fly while this one is multiplied)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                const int c = c0 + 16 * j + li;
+                bn[j] = c < ncol ? ld4(W + (size_t)c * ldw, kb + 16 + 4 * lk, K, vec) : (f4){0.0f, 0.0f, 0.0f, 0.0f};
+            }
+        }
+        const f4 a = *(const f4 *)(As + li * lda + kb + 4 * lk);
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kk], b[j][kk], acc[j], 0, 0, 0);
+        if (kb + 16 < kpad) {
+#pragma unroll
+            for (int j = 0; j < NT; ++j) b[j] = bn[j];
+        }
+    }
+}
+
+// one hidden layer of 16 rows in LDS: Y = relu(X W^T + b), wave w making the columns 128 w .. 128 w + 127
+__device__ __forceinline__ void play_layer(const float *X, const float *__restrict__ W, const float *__restrict__ bias, int K, int vec, float *Y,
+                                           int w, int lane) {
+    f4 acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = (f4){0.0f, 0.0f, 0.0f, 0.0f};
+    play_mm<8>(X, PS, W, K, K, (K + 15) / 16 * 16, 128 * w, HID, lane, vec, acc);
+    const int li = lane & 15, lk = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int col = 128 * w + 16 * j + li;
+        const float bj = bias[col];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Y[(4 * lk + r) * PS + col] = fmaxf(acc[j][r] + bj, 0.0f);
+    }
+}
+
+// the mu head of the 16 rows whose h2 is in X (LDS), then noise and clamp; R: 4 x 256 floats of LDS for the waves' partial tiles
+__device__ __forceinline__ void play_out(const Play &P, const float *X, float *R, int row0, int w, int lane) {
+    const Off o = offsets(P.D, P.A);
+    f4 acc[1] = {(f4){0.0f, 0.0f, 0.0f, 0.0f}};
+    play_mm<1>(X + 128 * w, PS, P.p + o.hw[0] + 128 * w, HID, 128, 128, 0, P.A, lane, P.pal, acc);
+    const int li = lane & 15, lk = lane >> 4;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) R[w * 256 + (4 * lk + r) * 16 + li] = acc[0][r];
+    __syncthreads();
+    const int t = threadIdx.x, r = t >> 4, a = t & 15, row = row0 + r;
+    if (row >= P.N || a >= P.A) return;
+    const float m = ((R[t] + R[256 + t]) + R[512 + t]) + R[768 + t] + P.p[o.hb[0] + a];
+    float act = m;
+    if (P.noise) act = __fadd_rn(m, __fmul_rn(expf(P.logstd[a]), P.noise[(size_t)row * P.A + a]));
+    P.clamped[(size_t)row * P.A + a] = fminf(fmaxf(act, -1.0f), 1.0f);
+    if (P.mu) P.mu[(size_t)row * P.A + a] = m;
+}
+
+// RunningMeanStd.forward in eval mode, as dwa_norm_rows
+__device__ __forceinline__ float play_norm(float x, const double *__restrict__ st, int D, int k) {
+    return fminf(fmaxf((x - (float)st[k]) / sqrtf((float)st[D + k] + NORM_EPS), -NORM_CLIP), NORM_CLIP);
+}
+
+__global__ __launch_bounds__(256) void dwa_play_rows(const Play P) {
+    __shared__ float X[PR * PS];          // the normalised rows, then h2
+    __shared__ float Y[PR * PS];          // h1, then the head's partial tiles
+    const int t = threadIdx.x, w = t >> 6, lane = t & 63, row0 = blockIdx.x * PR, D = P.D, dpad = (D + 15) / 16 * 16;
+    const Off o = offsets(D, P.A);
+    for (int e = t; e < PR * dpad; e += 256) {
+        const int r = e / dpad, k = e - r * dpad, row = row0 + r;
+        X[r * PS + k] = (row < P.N && k < D) ? play_norm(P.obs[(size_t)row * D + k], P.st, D, k) : 0.0f;
+    }
+    __syncthreads();
+    play_layer(X, P.p + o.w1[0], P.p + o.b1[0], D, P.pal && !(D & 3), Y, w, lane);
+    __syncthreads();
+    play_layer(Y, P.p + o.w2[0], P.p + o.b2[0], HID, P.pal, X, w, lane);
+    __syncthreads();
+    play_out(P, X, Y, row0, w, lane);
+}
+
+// one layer for N <= PLAY_SMALL_N rows: out[r][c0 .. c0 + 15] = relu(A[r] W^T + b) for the 16-column slice c0 = 16 blockIdx.x; the four
+// waves take a quarter of K's 16-deep blocks each.  NORM: A is the observation rows, normalised here (layer 1); else h1 (layer 2).
+template <int NORM>
+__global__ __launch_bounds__(256) void dwa_play_cols(const Play P) {
+    __shared__ float R[4][PLAY_SMALL_N * 16];
+    const int t = threadIdx.x, w = t >> 6, lane = t & 63, li = lane & 15, lk = lane >> 4, c0 = 16 * blockIdx.x, N = P.N;
+    const Off o = offsets(P.D, P.A);
+    const int K = NORM ? P.D : HID, nblk = (K + 15) / 16, kb0 = 16 * (nblk * w / 4), kb1 = 16 * (nblk * (w + 1) / 4);
+    const float *W = P.p + (NORM ? o.w1[0] : o.w2[0]), *bias = P.p + (NORM ? o.b1[0] : o.b2[0]);
+    const float *A = NORM ? P.obs : P.h1;
+    const int wvec = P.pal && (NORM ? !(K & 3) : 1), avec = NORM ? P.oal : 1;
+    const int rt = (N + 15) / 16;
+    f4 acc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] = (f4){0.0f, 0.0f, 0.0f, 0.0f};
+    for (int kb = kb0; kb < kb1; kb += 16) {
+        const int k = kb + 4 * lk;
+        const f4 b = ld4(W + (size_t)(c0 + li) * K, k, K, wvec);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (i < rt) {          // (wave-uniform)
+                const int row = 16 * i + li;
+                f4 a = (f4){0.0f, 0.0f, 0.0f, 0.0f};
+                if (row < N) {
+                    a = ld4(A + (size_t)row * K, k, K, avec);
+                    if (NORM) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) a[q] = k + q < K ? play_norm(a[q], P.st, K, k + q) : 0.0f;
+                    }
+                }
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kk], b[kk], acc[i], 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) R[w][(16 * i + 4 * lk + r) * 16 + li] = acc[i][r];
+    __syncthreads();
+    float *out = NORM ? P.h1 : P.h2;
+    for (int e = t; e < N * 16; e += 256) {
+        const int r = e >> 4, c = e & 15;
+        out[(size_t)r * HID + c0 + c] = fmaxf(((R[0][e] + R[1][e]) + R[2][e]) + R[3][e] + bias[c0 + c], 0.0f);
+    }
+}
+
+// the head for N <= PLAY_SMALL_N rows: h2 from the workspace into LDS, then play_out (one workgroup per 16 rows)
+__global__ __launch_bounds__(256) void dwa_play_head(const Play P) {
+    __shared__ float X[PR * PS];
+    __shared__ float R[4 * 256];
+    const int t = threadIdx.x, row0 = blockIdx.x * PR;
+    for (int e = t; e < PR * HID; e += 256) {
+        const int r = e / HID, k = e - r * HID;
+        X[r * PS + k] = row0 + r < P.N ? P.h2[(size_t)(row0 + r) * HID + k] : 0.0f;
+    }
+    __syncthreads();
+    play_out(P, X, R, row0, t >> 6, t & 63);
+}
+
 // ------------------------------------------------------------------------------------------------------------------------- host side
 int check_da(int D, int A) { return D >= 1 && D <= DWA_D_MAX && A >= 1 && A <= DWA_A_MAX; }
 int xl_of(int D) { return (D + 1 + 3) / 4 * 4; }
@@ -606,6 +787,32 @@ int dwa_opt(float *p, float *g, float *m, float *v, float *state, int32_t D, int
     if (done("dwa_opt_step")) return -1;
     hipLaunchKernelGGL(dwa_opt_tick, dim3(1), dim3(1), 0, s, state);
     return done("dwa_opt_tick");
+}
+
+int64_t dwa_play_workspace_bytes(int32_t N, int32_t D, int32_t A) {
+    if (!check_da(D, A) || N < 1) return -1;
+    return N <= PLAY_SMALL_N ? (int64_t)2 * N * HID * 4 : 0;
+}
+
+int dwa_play(const float *p, const double *obs_stats, const float *logstd, const float *obs, const float *noise, int32_t N, int32_t D, int32_t A,
+             float *clamped, float *mu, void *work, int64_t work_bytes, void *stream) {
+    if (!p || !obs_stats || !obs || !clamped || N < 1 || (noise && !logstd)) return fail("dwa_play: bad argument");
+    if (!check_da(D, A)) return fail("dwa_play: D must be in [1, 512] and A in [1, 16]");
+    const int64_t need = dwa_play_workspace_bytes(N, D, A);
+    if (work_bytes < need || (need > 0 && !work)) return fail("dwa_play: workspace too small (dwa_play_workspace_bytes)");
+    hipStream_t s = (hipStream_t)stream;
+    const int pal = !((uintptr_t)p & 15), oal = !((uintptr_t)obs & 15) && !(D & 3);
+    Play P{p, logstd, obs, noise, obs_stats, clamped, mu, (float *)work, (float *)work + (size_t)N * HID, N, D, A, pal, oal};
+    if (N > PLAY_SMALL_N) {
+        hipLaunchKernelGGL(dwa_play_rows, dim3((N + PR - 1) / PR), dim3(256), 0, s, P);
+        return done("dwa_play_rows");
+    }
+    hipLaunchKernelGGL((dwa_play_cols<1>), dim3(HID / 16), dim3(256), 0, s, P);
+    if (done("dwa_play_cols")) return -1;
+    hipLaunchKernelGGL((dwa_play_cols<0>), dim3(HID / 16), dim3(256), 0, s, P);
+    if (done("dwa_play_cols")) return -1;
+    hipLaunchKernelGGL(dwa_play_head, dim3((N + PR - 1) / PR), dim3(256), 0, s, P);
+    return done("dwa_play_head");
 }
 
 int dwa_gae(const float *done_, const float *values, const float *rewards, const float *next_values, int32_t H, int32_t N, float gamma,
