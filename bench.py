@@ -8,6 +8,10 @@ substeps + task logic).  Inputs (a pool of U(-1,1) action batches, seed 42) are 
 region; the timed region holds exactly K steps between barrier+synchronize pairs; rank 0 prints one JSON line.
 `--dump-outputs DIR` writes what the headline leg's last timed step returned; that leg then times the steps that follow a
 fixed pre-roll from reset(), so that with the same arguments it computes the same thing in every run.
+A plain run times the headline leg alone and prints its line.  `--full` adds every other measurement after it, each a run of
+its own: the step kernel alone on the stream (the roofline objects and alias_obs), a 256-step leg next to a short headline
+(long_run), and on one GPU 4096 envs, fresh actions, BASELINE config 5, the height field, config 3 (PPO), TocabiAMPLower and
+the CPU baseline, which the --no-* options skip.
 """
 from __future__ import annotations
 
@@ -211,6 +215,9 @@ def main():
     ap.add_argument("--steps", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=64)
     ap.add_argument("--envs-per-gpu", type=int, default=16384)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline leg, also run every secondary leg and roofline measurement (off: the headline alone); "
+                         "the --no-* options below skip legs of a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-also-4096", action="store_true", help="skip the secondary 4096-env measurement")
     ap.add_argument("--no-config5", action="store_true", help="skip the friction-DR + forced-pushes leg (BASELINE config 5)")
@@ -381,20 +388,37 @@ def main():
     wall_max = reduce_max(head["wall"])
     total_envs = args.envs_per_gpu * n_joined
     value = total_envs * args.steps / wall_max
-    # a short driver run (--steps 20 is 12 ms) says little by itself: time a longer region as well and report both
     long_run = None
-    if args.steps < 200:
-        r = run(args.envs_per_gpu, 256, 16)
-        w_l = reduce_max(r["wall"])
-        long_run = {"steps": 256, "value": total_envs * 256 / w_l, "ms_per_step": w_l / 256 * 1e3}
-    # the step kernel alone on the stream (zero-copy observation view): its mean launch duration is the roofline's denominator
-    alias = run(args.envs_per_gpu, max(args.steps, 256), args.warmup, alias_obs=True) if not plumbing else head
-    w_a = reduce_max(alias["wall"])
-    kernel_ms = alias["kernel_ms"]
-    n_a = max(args.steps, 256) if not plumbing else args.steps
+    if args.full:
+        # a short driver run (--steps 20 is 12 ms) says little by itself: time a longer region as well and report both
+        if args.steps < 200:
+            r = run(args.envs_per_gpu, 256, 16)
+            w_l = reduce_max(r["wall"])
+            long_run = {"steps": 256, "value": total_envs * 256 / w_l, "ms_per_step": w_l / 256 * 1e3}
+        # the step kernel alone on the stream (zero-copy observation view): its mean launch duration is the roofline's denominator
+        alias = run(args.envs_per_gpu, max(args.steps, 256), args.warmup, alias_obs=True) if not plumbing else head
+        w_a = reduce_max(alias["wall"])
+        kernel_ms = alias["kernel_ms"]
+        n_a = max(args.steps, 256) if not plumbing else args.steps
 
     out = None
     if rank == 0:
+        out = {
+            "metric": "env-steps/sec (whole node) DyrosDynamicWalk", "value": value, "unit": "env-steps/s",
+            "n_gpus": n_joined, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": wall_max / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic" if not plumbing else "plumbing-test (no kernel ran)",
+            "config": {"workload": "DyrosDynamicWalk random-action rollout, flat ground, mu=1, DR (mass/damping/armature) on, "
+                                   "resets on, in-kernel RNG, step() returns a fresh observation tensor (reference contract)",
+                       "num_envs_per_gpu": args.envs_per_gpu,
+                       "total_envs": total_envs, "substeps_per_step": 2, "dt": 0.002,
+                       "parallelism": "env-sharded x%d, no collective in step; RCCL all-gather of episode stats every %d steps" % (n_joined, HORIZON)},
+            "episodes": dict(head["episodes"], finished_total=head["resets"]),
+            "head_leg_device_ms_per_step": head["kernel_ms"],          # HIP events around the same K steps (no host latency at either end)
+        }
+        if plumbing:
+            out["valid"] = False
+    if rank == 0 and args.full:
         kinfo = head["kinfo"]
         achieved = A_STEP_BYTES * args.envs_per_gpu / (kernel_ms * 1e-3) / 1e9
         traffic, lane_slots, traffic_note = None, None, None
@@ -412,31 +436,18 @@ def main():
                 traffic_note = "profiles/pmc_traffic.json unreadable: %s" % e
         useful_flops = FLOPS_PER_ENV_STEP * args.envs_per_gpu
         valu = useful_flops / (kernel_ms * 1e-3) / 1e12
-        out = {
-            "metric": "env-steps/sec (whole node) DyrosDynamicWalk", "value": value, "unit": "env-steps/s",
-            "n_gpus": n_joined, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": wall_max / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic" if not plumbing else "plumbing-test (no kernel ran)",
-            "config": {"workload": "DyrosDynamicWalk random-action rollout, flat ground, mu=1, DR (mass/damping/armature) on, "
-                                   "resets on, in-kernel RNG, step() returns a fresh observation tensor (reference contract)",
-                       "num_envs_per_gpu": args.envs_per_gpu,
-                       "total_envs": total_envs, "substeps_per_step": 2, "dt": 0.002,
-                       "parallelism": "env-sharded x%d, no collective in step; RCCL all-gather of episode stats every %d steps" % (n_joined, HORIZON)},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "kernel": kinfo.get("kernels", "dw_k_step"), "kernel_ms": kernel_ms,
-                         "algorithmic_bytes_per_launch": A_STEP_BYTES * args.envs_per_gpu,
-                         "kernel_source_hash": kernel_source_hash()},
-            # the second roof: useful flops of the step (per-phase count in DESIGN.md section 6) against
-            # the fp32 vector peak; lane_slots_per_env_step comes from the SQ_INSTS_VALU PMC pass when one is committed
-            "roofline_valu": {"bound": "valu_f32", "achieved": valu, "peak": VALU_PEAK_TF, "unit": "TFLOP/s",
-                              "frac": valu / VALU_PEAK_TF, "useful_flops_per_env_step": FLOPS_PER_ENV_STEP,
-                              "lane_slots_per_env_step": lane_slots},
-            "alias_obs": {"value": total_envs * n_a / w_a, "ms_per_step": w_a / n_a * 1e3,
-                          "note": "cfg sim.mi355.alias_obs: step() returns the view of obs_buf (no copy kernel on the stream)"},
-            "episodes": dict(head["episodes"], finished_total=head["resets"]),
-            "head_leg_device_ms_per_step": head["kernel_ms"],          # HIP events around the same K steps (no host latency at either end)
-        }
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                           "kernel": kinfo.get("kernels", "dw_k_step"), "kernel_ms": kernel_ms,
+                           "algorithmic_bytes_per_launch": A_STEP_BYTES * args.envs_per_gpu,
+                           "kernel_source_hash": kernel_source_hash()}
+        # the second roof: useful flops of the step (per-phase count in DESIGN.md section 6) against
+        # the fp32 vector peak; lane_slots_per_env_step comes from the SQ_INSTS_VALU PMC pass when one is committed
+        out["roofline_valu"] = {"bound": "valu_f32", "achieved": valu, "peak": VALU_PEAK_TF, "unit": "TFLOP/s",
+                                "frac": valu / VALU_PEAK_TF, "useful_flops_per_env_step": FLOPS_PER_ENV_STEP,
+                                "lane_slots_per_env_step": lane_slots}
+        out["alias_obs"] = {"value": total_envs * n_a / w_a, "ms_per_step": w_a / n_a * 1e3,
+                            "note": "cfg sim.mi355.alias_obs: step() returns the view of obs_buf (no copy kernel on the stream)"}
         if lane_slots and torch.cuda.is_available():
             # what binds the kernel at this size: the SIMD's vector-instruction issue.  Floor = the kernel's own VALU instruction
             # count (PMC) at the measured issue rate of plain fp32 instructions, spread evenly over the device's SIMDs
@@ -456,11 +467,9 @@ def main():
                                     "kernel": kinfo.get("kernels", "dw_k_step").replace("step", "simulate"), "kernel_ms": alias["sim_ms"],
                                     "algorithmic_bytes_per_launch": A_PHYS_BYTES * args.envs_per_gpu,
                                     "env_substeps_per_s": args.envs_per_gpu / (alias["sim_ms"] * 1e-3)}
-        if plumbing:
-            out["valid"] = False
         if long_run:
             out["long_run"] = long_run
-    if world == 1 and not plumbing:
+    if args.full and world == 1 and not plumbing:
         n2 = max(args.steps, 256)
         if not args.no_also_4096:               # BASELINE config 2
             r2 = run(4096, n2, args.warmup)
@@ -557,7 +566,7 @@ def main():
             except Exception as e:
                 out["amp_lower"] = {"error": str(e)}
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and not plumbing:
+        if args.full and world == 1 and not args.no_cpu_baseline and not plumbing:
             try:
                 out["cpu_baseline"] = cpu_baseline()
             except Exception as e:          # the oracle is a checker; the bench line stands without it

@@ -26,7 +26,7 @@ def _run(extra, env_extra=None, timeout=300, steps=6):
 
 
 def test_bare_invocation_spawns_two_ranks_and_relays_one_line():
-    p = _run(["--gpus", "2"])
+    p = _run(["--gpus", "2", "--full"])
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout
@@ -38,7 +38,7 @@ def test_bare_invocation_spawns_two_ranks_and_relays_one_line():
     assert out["episodes"]["envs_with_episode"] == 32          # the all-gather saw both ranks' blocks
     assert abs(out["episodes"]["mean_episode_length"] - 1.5) < 1e-9     # rank 0 wrote 1.0, rank 1 wrote 2.0
     assert out["value"] > 0 and abs(out["value"] - 32 * 6 / (out["ms_per_step"] * 6e-3)) / out["value"] < 1e-6
-    # the contract's two roofline objects are always there (numbers mean nothing on the plumbing env)
+    # with --full the two roofline objects are there (numbers mean nothing on the plumbing env)
     assert {"bound", "achieved", "peak", "unit", "frac", "traffic", "kernel"} <= set(out["roofline"])
     assert out["roofline"]["bound"] == "hbm" and out["roofline"]["peak"] == 8000.0 and out["roofline"]["unit"] == "GB/s"
     assert {"bound", "achieved", "peak", "frac", "useful_flops_per_env_step", "lane_slots_per_env_step"} <= set(out["roofline_valu"])
@@ -52,6 +52,21 @@ def test_single_rank_needs_no_launcher():
     assert json.loads(p.stdout.strip().splitlines()[-1])["n_gpus"] == 1
 
 
+def test_plain_run_times_the_headline_leg_alone():
+    """Without --full the line carries the headline and what its own leg measured, and no leg of --full ran: no long_run
+    beside a short headline, no roofline objects from the step kernel's own leg."""
+    p = _run(["--gpus", "2"], steps=100)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout
+    out = json.loads(lines[0])
+    assert out["metric"].startswith("env-steps/sec") and out["unit"] == "env-steps/s" and out["dtype"] == "f32"
+    assert out["higher_is_better"] is True and out["n_gpus"] == 2 and out["steps"] == 100
+    assert out["value"] > 0 and abs(out["value"] - 32 * 100 / (out["ms_per_step"] * 100e-3)) / out["value"] < 1e-6
+    assert out["episodes"]["envs_with_episode"] == 32 and out["head_leg_device_ms_per_step"] > 0
+    assert not {"long_run", "roofline", "roofline_valu", "roofline_phys", "alias_obs", "cpu_baseline"} & set(out), sorted(out)
+
+
 def test_contradicting_world_size_is_an_error():
     p = _run(["--gpus", "4"], env_extra={"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert p.returncode != 0 and "contradicts WORLD_SIZE" in p.stderr
@@ -62,8 +77,8 @@ def test_short_head_leg_reads_like_the_long_leg():
     tell the same ms/step (the 20-step headline read 12 % under its own long leg because the warm-up was
     counted in steps).  On the plumbing env a step is a 1 ms busy wait, so this checks the SHAPE of run(): warm by wall time,
     events / gather exercised before the timer, exactly K steps inside it (5 % here: a host clock under other work is noisy; on the GPU
-    the two legs read within 2 %)."""
-    p = _run(["--gpus", "1"], steps=100)
+    the two legs read within 2 %).  The long leg is one of --full's."""
+    p = _run(["--gpus", "1", "--full"], steps=100)
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads(p.stdout.strip().splitlines()[-1])
     assert out["steps"] == 100 and out["long_run"]["steps"] == 256
