@@ -232,7 +232,8 @@ POLICY_COPY_PER_UPDATE = os.environ.get("DW_PPO_POLICY_COPY_PER_UPDATE", "0") ==
 
 
 def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cfg=None, max_epochs=None, env=None,
-          rank=0, world=1, seed=42, graph_rollout=False, graph_update=False, fused_update=False, fused_collective=None, global_gate=False):
+          rank=0, world=1, seed=42, graph_rollout=False, graph_update=False, fused_update=False, fused_collective=None, global_gate=False,
+          checkpoint=None, output_dir=None, save_frequency=0, experiment="DyrosDynamicWalk"):
     """`epochs` PPO epochs of the DYROS configuration on `num_envs` envs of this rank.  Returns one stats dict per epoch.
     graph_rollout: one rollout step (policy inference, sampling, env step, bookkeeping) is captured once in a hipGraph and
     replayed `horizon` times per epoch -- possible because dw_step_dev keeps the step counter in device memory, so a replayed
@@ -247,7 +248,13 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
     collective is refused, or with DW_PPO_GRAPH_COLLECTIVE=0, the update is two replayed graphs with the collective enqueued between them.
     fused_collective=True runs that sharded form of the update on ONE rank too (tests: same bits as the plain four launches).
     global_gate (sharded runs): once per horizon the ranks' push-perturbation gates latch on the means over ALL envs
-    (env.sync_perturbation_gate: one all-reduce of 3 doubles) instead of per rank as in the reference's Horovod layout."""
+    (env.sync_perturbation_gate: one all-reduce of 3 doubles) instead of per rank as in the reference's Horovod layout.
+    checkpoint: a file of isaacgymdyros_amd/ppo_checkpoint.py (ours or the reference learner's) restored before any graph is captured -- weights,
+    both optimisers (or the fused update's moments, steps and learning rates) and the loss scale; the epochs then continue from the file's epoch + 1
+    with the schedule's lr and sigma of those epoch numbers, and `frame` continues.  Every rank restores the same file.
+    output_dir (rank 0 writes): <output_dir>/<experiment>/nn/<experiment>_<epoch>.pth every save_frequency epochs (0: never) and
+    <experiment>.pth after the last epoch.  The reference's last_..._ep_<n>_rew_<r> and best-reward names (a2c_common_dyros.py:1036-1075) need
+    per-episode returns, which this loop does not track; the names here are those of examples/amp_consumer.py."""
     from isaacgymdyros_amd.config import default_cfg
     from isaacgymdyros_amd.dyros_dynamic_walk import DyrosDynamicWalk
     cfg = cfg or TRAIN_CFG
@@ -289,6 +296,22 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
     sched = LinearLR(c["learning_rate"], c["learning_rate_min"], max_epochs)
     amp = bool(c["mixed_precision"]) and str(device).startswith("cuda")
     scaler = torch.amp.GradScaler("cuda", enabled=amp)
+    start, frame = 0, 0
+    if checkpoint:
+        from isaacgymdyros_amd import ppo_checkpoint as PK
+        # (before any capture: the weights are written in place -- into the fused update's master buffer, whose copies are refreshed --, and a
+        #  capturable Adam keeps its device lr tensor)
+        got = (PK.restore(checkpoint, net, fused=fused) if fused is not None else
+               PK.restore(checkpoint, net, opt_actor=opt_a, opt_critic=opt_c, scaler=scaler))
+        start, frame = got["epoch"], got["frame"]
+        if rank == 0:
+            log("restored %s: epoch %d, frame %d" % (checkpoint, start, frame))
+
+    def save(path, epoch):
+        from isaacgymdyros_amd import ppo_checkpoint as PK
+        kw = dict(fused=fused) if fused is not None else dict(opt_actor=opt_a, opt_critic=opt_c, scaler=scaler)
+        PK.save(path, net, epoch, frame, lr0=float(c["learning_rate"]), lr_min=float(c["learning_rate_min"]), max_epochs=max_epochs, **kw)
+    nn_dir = os.path.join(output_dir, experiment, "nn") if output_dir else None
     names = list(env.extras.get("reward_names", []))
     obs = env.reset()["obs"].clone()
     dones = torch.zeros(N, device=device)
@@ -374,7 +397,8 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
             for _ in range(roll_chain):
                 rollout_step()
         obs, dones = g_obs, g_dones
-    for ep in range(1, epochs + 1):
+    ep = start
+    for ep in range(start + 1, start + epochs + 1):
         net.update_action_noise((max_epochs - ep) / max_epochs)                 # a2c_common_dyros.py:985
         lr = sched(ep)
         if fused is not None:
@@ -568,10 +592,16 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
                  mean_episode_length=float(env.epi_len_log[fin].mean()) if int(fin.sum()) else 0.0)
         if os.environ.get("DW_PPO_TIMES") and fused is not None:
             s.update(play_ms=1e3 * play_time, prep_ms=1e3 * t_prep, update_ms=1e3 * (total - play_time - t_prep))
+        frame += H * N
+        s["frame"] = frame
         stats.append(s)
         if rank == 0:
             log("epoch %(epoch)d: fps step %(step_fps).3g  step+inference %(play_fps).3g  total %(total_fps).3g  mean reward %(mean_reward).3f  "
                 "a_loss %(a_loss).3g  c_loss %(c_loss).3g  kl %(kl).2g  lr %(lr).2g  log-sigma %(sigma).3f  episode length %(mean_episode_length).1f" % s)
+        if nn_dir and rank == 0 and save_frequency > 0 and ep % save_frequency == 0:
+            save(os.path.join(nn_dir, "%s_%d.pth" % (experiment, ep)), ep)
+    if nn_dir and rank == 0:
+        save(os.path.join(nn_dir, experiment + ".pth"), ep)
     if own_env:
         env.close()
     return stats
@@ -585,12 +615,17 @@ def main():
     ap.add_argument("--fused", action="store_true", help="rollout step and minibatch update replayed from hipGraphs, the update, the rollout's "
                     "forward, its bookkeeping and GAE as the HIP kernels of include/dyros_ppo.h (14.7 M frames/s at 16384 envs on one GPU instead of 0.35 M "
                     "eager); under torchrun every update carries one RCCL all-reduce of the gradient bucket")
+    ap.add_argument("--checkpoint", default=None, help="resume from this checkpoint (isaacgymdyros_amd/ppo_checkpoint.py; ours or the reference learner's)")
+    ap.add_argument("--output-dir", default=None, help="write checkpoints to <dir>/DyrosDynamicWalk/nn/ (rank 0)")
+    ap.add_argument("--save-frequency", type=int, default=None, help="epochs between numbered checkpoints (default: the yaml's 100 with --output-dir)")
     a = ap.parse_args()
+    save_frequency = a.save_frequency if a.save_frequency is not None else (100 if a.output_dir else 0)
     from isaacgymdyros_amd import dist as dwdist
     rank, local_rank, world = dwdist.init_from_env("nccl")
     dev = "cuda:%d" % local_rank
     torch.cuda.set_device(local_rank)
-    train(a.num_envs, a.epochs, a.horizon, device=dev, rank=rank, world=world, graph_rollout=a.fused, fused_update=a.fused)
+    train(a.num_envs, a.epochs, a.horizon, device=dev, rank=rank, world=world, graph_rollout=a.fused, fused_update=a.fused,
+          checkpoint=a.checkpoint, output_dir=a.output_dir, save_frequency=save_frequency)
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -1,0 +1,87 @@
+#!/usr/bin/env python3
+"""Plays a DyrosDynamicWalk PPO policy from a checkpoint, as the reference's play path does (paths relative to
+python/IsaacGymEnvs/isaacgymenvs/learning/rl_games_custom): restore, the text export TOCABI's controller loads (torch_runner_dyros.py:133-150:
+every model tensor as <name with . -> _>.txt), then rl_games' PpoPlayerContinuous loop, restated here as examples/amp_player.py restates
+CommonPlayer (rl_games is not part of the reference's checkout): the policy's action, env.step (which resets finished envs itself), the reward
+and the steps summed per env; on done envs `reward: ... steps: ...` (the means over the envs done at that step), at the end
+`av reward: ... av steps: ...`.
+
+The action is WalkPolicy.play (isaacgymdyros_amd/walk_policy.py): the actor in eval mode, deterministic clamp(mu, -1, 1) -- rescale_actions is the
+identity on this task's +-1 action space (tasks/base/vec_task.py:95) -- or, with --stochastic, clamp(mu + exp(sigma) noise, -1, 1).  On
+--policy-backend hip that is dwp_play.  An episode is 32 s at 4 ms per policy step (8000 steps); --max-steps defaults to 10000, so every game can
+end on its own.
+"""
+from __future__ import annotations
+
+import argparse
+import math
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from isaacgymdyros_amd import ppo_checkpoint as PK          # noqa: E402
+
+
+def run(args):
+    from isaacgymdyros_amd.config import default_cfg
+    from isaacgymdyros_amd.dyros_dynamic_walk import DyrosDynamicWalk
+    dev = torch.device(args.device)
+    env = DyrosDynamicWalk(default_cfg(args.num_envs, args.device), args.device, 0, True)
+    ck = PK.load(args.checkpoint)
+    n_obs, n_act = int(ck["model"][PK.PREFIX + "actor_mlp.0.weight"].shape[1]), int(ck["model"][PK.PREFIX + "mu.weight"].shape[0])
+    if (n_obs, n_act) != (env.num_obs, env.num_acts):
+        raise SystemExit("checkpoint: %d observations / %d actions, the task has %d / %d" % (n_obs, n_act, env.num_obs, env.num_acts))
+    if args.export_dir:
+        PK.export_txt(ck, args.export_dir)
+    pol = PK.load_policy(ck, dev, backend=args.policy_backend)
+    N, games_played, sum_rewards, sum_steps = env.num_envs, 0, 0.0, 0.0
+    obs = env.reset()["obs"]
+    cr = torch.zeros(N, device=dev)
+    steps = torch.zeros(N, device=dev)
+    for _n in range(args.max_steps):
+        noise = torch.randn(N, n_act, device=dev) if args.stochastic else None
+        action, _mu = pol.play(obs.contiguous(), noise)
+        o, r, done, _info = env.step(action)
+        obs = o["obs"]
+        cr += r.view(N)
+        steps += 1
+        idx = done.nonzero(as_tuple=False).view(-1)
+        k = int(idx.numel())
+        if k > 0:
+            games_played += k
+            cur_r, cur_s = float(cr[idx].sum()), float(steps[idx].sum())
+            keep = 1.0 - done.float().view(N)
+            cr, steps = cr * keep, steps * keep
+            sum_rewards += cur_r
+            sum_steps += cur_s
+            print("reward:", cur_r / k, "steps:", cur_s / k, flush=True)
+            if games_played >= args.games:
+                break
+    env.close()
+    if games_played == 0:
+        raise SystemExit("no game ended within --max-steps %d" % args.max_steps)
+    av_r, av_s = sum_rewards / games_played, sum_steps / games_played
+    print("av reward:", av_r, "av steps:", av_s, flush=True)
+    if not (math.isfinite(av_r) and math.isfinite(av_s)):
+        raise SystemExit("non-finite average")
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--checkpoint", required=True, help="a checkpoint of examples/ppo_consumer.py --output-dir (or the reference learner's)")
+    ap.add_argument("--num-envs", type=int, default=64)
+    ap.add_argument("--games", type=int, default=100)
+    ap.add_argument("--max-steps", type=int, default=10000)
+    ap.add_argument("--stochastic", action="store_true", help="sample mu + exp(sigma) noise instead of the deterministic mu")
+    ap.add_argument("--policy-backend", default="hip", choices=["hip", "torch"])
+    ap.add_argument("--export-dir", default=None, help="write the model tensors as the reference's text files here")
+    ap.add_argument("--device", default="cuda:0")
+    run(ap.parse_args())
+
+
+if __name__ == "__main__":
+    main()

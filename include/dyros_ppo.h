@@ -51,7 +51,7 @@
 extern "C" {
 #endif
 
-#define DWP_ABI_VERSION 8
+#define DWP_ABI_VERSION 9
 #define DWP_IN    487   /* observation words (DyrosDynamicWalk.yaml numObservations)        */
 #define DWP_INP   512   /* ... padded: rows of the input matrix and of W1 (zero columns), so that the GEMMs see aligned rows */
 #define DWP_HID   256   /* cfg/train/DyrosDynamicWalkPPO.yaml:27 units [256, 256]            */
@@ -195,6 +195,17 @@ int dwp_rollout_post(const float *rew, const float *value, const int64_t *time_o
  * in operand order (dwp_retile32 once, then kept by dwp_adam).  Any N >= 1. */
 int dwp_policy(const float *obs, const float *p, const float *p32f, int32_t N, float *mu, float *value, void *stream);
 int dwp_retile32(const float *p, float *p32f, void *stream);
+
+/* The walk actor at play time (ABI 9): the actor alone, eval mode, fp32 on v_mfma_f32_16x16x4_f32, from the DWP layout as
+ * FusedPpoUpdate keeps it -- p: the fp32 masters (the biases), p32f: the weights in dwp_policy's operand order (dwp_retile32).  For obs [N][IN]:
+ *   mu [N][ACT] = W3 relu(W2 relu(W1 obs + b1) + b2) + b3 of the actor (or NULL),
+ *   clamped [N][ACT] = clamp(mu, -1, 1), or clamp(mu + exp(logstd) * noise, -1, 1) when noise [N][ACT] is given (logstd [ACT] then too).
+ * N > 64: one launch of dwp_policy's tiles for the actor only; its mu is dwp_policy's mu bit for bit.  N <= 64: each layer split into 16-column
+ * workgroups whose eight waves split K and add their parts in wave order, h1 and h2 in `work` (work_floats floats, at least
+ * dwp_play_work_floats(N)).  No atomics: a replayed graph gives the eager bits.  Arguments are checked before anything is launched. */
+int dwp_play_work_floats(int32_t N);          /* floats of workspace dwp_play needs for N rows: 0 for N > 64, -1 for N < 1 */
+int dwp_play(const float *p, const float *p32f, const float *logstd, const float *obs, const float *noise, int32_t N, float *clamped, float *mu,
+             float *work, int32_t work_floats, void *stream);
 
 /* p16f from p16 (all weights; after construction or after loading parameters) */
 int dwp_retile(const uint16_t *p16, uint16_t *p16f, void *stream);

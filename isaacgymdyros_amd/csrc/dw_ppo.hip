@@ -1335,6 +1335,163 @@ __global__ __launch_bounds__(64 * PWPB) void k_policy(const float *__restrict__ 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ dwp_play: the walk actor at play time
+// The actor alone, eval mode, fp32, from the layout dwp_policy reads (p: biases, p32f: weights in operand order).  Two forms:
+//   N > WPLAY_SMALL_N  k_wplay_rows: k_policy's grid for the actor only -- the same tiles, the same k order, the same head -- with the noise and
+//                      the clamp in the head's epilogue, so its mu is dwp_policy's mu bit for bit
+//   N <= WPLAY_SMALL_N k_wplay_cols<1 | 2 | 3>: one layer per launch, a 16-column tile per workgroup (16 workgroups share the 0.5 MB of W1 instead
+//                      of one reading all 0.79 MB of the actor), its eight waves split K and their parts are added in wave order; h1 and h2 go
+//                      through the workspace with their columns permuted as perm16, so a lane's four k of the next layer are one 16-byte load
+// No atomics, no grid barrier: a replayed graph gives the eager bits.
+constexpr int WPLAY_SMALL_N = 64;          // the largest N of the column form (four row tiles)
+constexpr int CWPB = 8;                    // waves per workgroup of the column form
+struct WPlay {
+    const float *p, *p32f, *logstd, *obs, *noise;
+    float *clamped, *mu, *h1, *h2;
+    int N;
+};
+
+// action a of row `row` from its mean m: the noise (if any), the clamp, and mu (if asked for)
+__device__ __forceinline__ void wplay_out(const WPlay &P, int row, int a, float m) {
+#pragma clang fp contract(off)          // (this unit contracts by default: mu + sigma * noise as two roundings, as torch computes it)
+    float act = m;
+    if (P.noise) {
+        const float sd = expf(P.logstd[a]), sn = sd * P.noise[(size_t)row * ACT + a];
+        act = m + sn;
+    }
+    P.clamped[(size_t)row * ACT + a] = fminf(fmaxf(act, -1.0f), 1.0f);
+    if (P.mu) P.mu[(size_t)row * ACT + a] = m;
+}
+
+// k_policy with net = 0 (kept as a copy: k_policy's own code stays as it is); only the head's epilogue differs
+__global__ __launch_bounds__(64 * PWPB) void k_wplay_rows(const WPlay P) {
+    __shared__ float Xs[MT * XS32];          // the input rows; after the first layer: the second hidden layer
+    __shared__ float H1s[MT * HS32];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r0 = blockIdx.x * MT, N = P.N;
+    const int nt0 = PNTW * wv, cr = lane & 15, g = lane >> 4;
+    const float *W1 = P.p32f + G_W1, *W2 = P.p32f + G_W2, *W3 = P.p32f + G_W3;
+    const float *b1 = P.p + NWT, *b2 = P.p + NWT + NB1, *b3 = P.p + NWT + NB1 + NB2;
+    {
+        const float *src = P.obs + (size_t)r0 * IN;
+        constexpr int CPT = INP / (64 * PWPB);
+        const int rmax = N - 1 - r0;          // (rows past the end read the last row again; nothing of theirs is stored)
+        float v[CPT][MT];
+#pragma unroll
+        for (int u = 0; u < CPT; ++u) {
+            const int c = tid + 64 * PWPB * u, cl = c < IN ? c : 0;
+#pragma unroll
+            for (int r = 0; r < MT; ++r) { const int rr = r < rmax ? r : rmax; v[u][r] = src[(size_t)rr * IN + cl]; }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < CPT; ++u) {
+            const int c = tid + 64 * PWPB * u, q = perm16(c);
+#pragma unroll
+            for (int r = 0; r < MT; ++r) Xs[r * XS32 + q] = c < IN ? v[u][r] : 0.0f;
+        }
+        __syncthreads();
+    }
+    f4 acc[MR][PNTW];
+    float bia[PNTW];
+#pragma unroll
+    for (int t = 0; t < PNTW; ++t) bia[t] = b1[16 * (nt0 + t) + cr];
+    mfma32_rows<INP / 16, XS32, NTL, PNTW, 3>(Xs, W1, nt0, acc, lane);
+#pragma unroll
+    for (int mr = 0; mr < MR; ++mr)
+#pragma unroll
+        for (int t = 0; t < PNTW; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) H1s[(16 * mr + 4 * g + r) * HS32 + perm16(16 * (nt0 + t) + cr)] = fmaxf(acc[mr][t][r] + bia[t], 0.0f);
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < PNTW; ++t) bia[t] = b2[16 * (nt0 + t) + cr];
+    mfma32_rows<HID / 16, HS32, NTL, PNTW, 3>(H1s, W2, nt0, acc, lane);
+    float *H2s = Xs;          // [MT][HS32]
+#pragma unroll
+    for (int mr = 0; mr < MR; ++mr)
+#pragma unroll
+        for (int t = 0; t < PNTW; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) H2s[(16 * mr + 4 * g + r) * HS32 + perm16(16 * (nt0 + t) + cr)] = fmaxf(acc[mr][t][r] + bia[t], 0.0f);
+    __syncthreads();
+    if (wv < MR) {
+        const int ar = lane & 15;
+        const f4 *wl = reinterpret_cast<const f4 *>(W3) + lane;
+        f4 o = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int kg = 0; kg < HID / 16; ++kg) {
+            const f4 bq = wl[kg * 64];
+            const f4 aq = *reinterpret_cast<const f4 *>(H2s + (16 * wv + ar) * HS32 + 16 * kg + 4 * g);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o = __builtin_amdgcn_mfma_f32_16x16x4f32(aq[j], bq[j], o, 0, 0, 0);
+        }
+        const float bias = b3[cr];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = r0 + 16 * wv + 4 * g + r;
+            if (row < N && cr < ACT) wplay_out(P, row, cr, o[r] + bias);
+        }
+    }
+}
+
+// one layer for N <= WPLAY_SMALL_N rows: the 16 output columns of tile blockIdx.x (LAYER 3: the head's one tile).  Wave w takes the k groups
+// [KG w / CWPB, KG (w + 1) / CWPB); the waves' partial tiles are added in wave order.  Input: obs rows (LAYER 1: k < IN, zeros beyond), or h1 / h2
+// from the workspace (perm16 columns).  Output: relu(. + b) into h1 / h2 (LAYER 1 / 2), or the actions (LAYER 3).
+template <int LAYER>
+__global__ __launch_bounds__(64 * CWPB) void k_wplay_cols(const WPlay P) {
+    constexpr int KG = (LAYER == 1 ? INP : HID) / 16, NT = LAYER == 3 ? 1 : HID / 16, KPW = KG / CWPB;
+    static_assert(KG % CWPB == 0, "whole k groups per wave");
+    __shared__ float R[CWPB][WPLAY_SMALL_N * 16];
+    const int t = threadIdx.x, w = t >> 6, lane = t & 63, li = lane & 15, g = lane >> 4, nt = blockIdx.x, N = P.N, rt = (N + 15) / 16;
+    const f4 *wl = reinterpret_cast<const f4 *>(P.p32f + (LAYER == 1 ? G_W1 : LAYER == 2 ? G_W2 : G_W3)) + nt * 64 + lane;
+    const float *src = LAYER == 2 ? P.h1 : P.h2;
+    const int kg0 = KPW * w;
+    f4 acc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] = (f4){0.0f, 0.0f, 0.0f, 0.0f};
+    f4 b[KPW];
+#pragma unroll
+    for (int q = 0; q < KPW; ++q) b[q] = wl[(kg0 + q) * NT * 64];
+#pragma unroll
+    for (int q = 0; q < KPW; ++q) {
+        const int kg = kg0 + q;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (i < rt) {          // (uniform over the workgroup)
+                const int row = 16 * i + li;
+                f4 a = (f4){0.0f, 0.0f, 0.0f, 0.0f};
+                if (row < N) {
+                    if (LAYER == 1) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) { const int k = 16 * kg + 4 * j + g; a[j] = k < IN ? P.obs[(size_t)row * IN + k] : 0.0f; }
+                    } else {
+                        a = *reinterpret_cast<const f4 *>(src + (size_t)row * HID + 16 * kg + 4 * g);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[q][j], acc[i], 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) R[w][(16 * i + 4 * g + r) * 16 + li] = acc[i][r];
+    __syncthreads();
+    for (int e = t; e < N * 16; e += 64 * CWPB) {
+        const int r = e >> 4, c = e & 15, col = 16 * nt + c;
+        float s = R[0][e];
+#pragma unroll
+        for (int q = 1; q < CWPB; ++q) s += R[q][e];
+        if (LAYER == 3) {
+            if (c < ACT) wplay_out(P, r, c, s + P.p[NWT + NB1 + NB2 + c]);
+        } else {
+            float *out = LAYER == 1 ? P.h1 : P.h2;
+            out[(size_t)r * HID + perm16(col)] = fmaxf(s + P.p[NWT + (LAYER == 1 ? 0 : NB1) + col], 0.0f);
+        }
+    }
+}
+
 int done(const char *who) {
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : fail_hip(who, e);
@@ -1493,6 +1650,27 @@ int dwp_policy(const float *obs, const float *p, const float *p32f, int32_t N, f
     if (!obs || !p || !p32f || !mu || !value || N < 1) return fail("dwp_policy: bad argument");
     hipLaunchKernelGGL(k_policy, dim3((N + MT - 1) / MT, 2), dim3(64 * PWPB), 0, (hipStream_t)stream, obs, p, p32f, N, mu, value);
     return done("dwp_policy");
+}
+
+int dwp_play_work_floats(int32_t N) { return N < 1 ? -1 : N <= WPLAY_SMALL_N ? 2 * N * HID : 0; }
+
+int dwp_play(const float *p, const float *p32f, const float *logstd, const float *obs, const float *noise, int32_t N, float *clamped, float *mu,
+             float *work, int32_t work_floats, void *stream) {
+    if (N < 1 || !p || !p32f || !obs || !clamped || (noise && !logstd)) return fail("dwp_play: bad argument");
+    const int need = dwp_play_work_floats(N);
+    if (work_floats < need || (need > 0 && !work)) return fail("dwp_play: workspace too small (dwp_play_work_floats)");
+    hipStream_t s = (hipStream_t)stream;
+    const WPlay P{p, p32f, logstd, obs, noise, clamped, mu, work, need > 0 ? work + (size_t)N * HID : nullptr, N};
+    if (N > WPLAY_SMALL_N) {
+        hipLaunchKernelGGL(k_wplay_rows, dim3((N + MT - 1) / MT), dim3(64 * PWPB), 0, s, P);
+        return done("dwp_play");
+    }
+    hipLaunchKernelGGL(k_wplay_cols<1>, dim3(HID / 16), dim3(64 * CWPB), 0, s, P);
+    if (done("dwp_play")) return -1;
+    hipLaunchKernelGGL(k_wplay_cols<2>, dim3(HID / 16), dim3(64 * CWPB), 0, s, P);
+    if (done("dwp_play")) return -1;
+    hipLaunchKernelGGL(k_wplay_cols<3>, dim3(1), dim3(64 * CWPB), 0, s, P);
+    return done("dwp_play");
 }
 
 int dwp_sizeof_mlp(void) { return (int)sizeof(DwpMlp); }

@@ -41,7 +41,7 @@ def _constants() -> dict:
 
 
 K = _constants()
-EXPORTS = ["abi_version", "last_error", "sizeof_mlp", "stage_obs", "bias_relu", "loss", "relu_bwd", "grad_stats", "grad_bucket", "adam", "adam_finish", "stats_adam_finish", "finish", "retile", "mlp", "wgrad", "gae", "rollout_pre", "rollout_post", "policy", "retile32"]
+EXPORTS = ["abi_version", "last_error", "sizeof_mlp", "stage_obs", "bias_relu", "loss", "relu_bwd", "grad_stats", "grad_bucket", "adam", "adam_finish", "stats_adam_finish", "finish", "retile", "mlp", "wgrad", "gae", "rollout_pre", "rollout_post", "policy", "retile32", "play", "play_work_floats"]
 IN, INP, HID, OUTP, ACT = K["DWP_IN"], K["DWP_INP"], K["DWP_HID"], K["DWP_OUTP"], K["DWP_ACT"]
 NW1, NW2, NW3 = 2 * HID * INP, 2 * HID * HID, 2 * OUTP * HID
 NWT = NW1 + NW2 + NW3
@@ -93,6 +93,8 @@ def declare(lib: C.CDLL) -> dict:
     api["adam"] = fn("adam", C.c_int, P, P, P, P, P, P, P, P, C.c_float, P, P, C.c_int32, P, P)
     api["policy"] = fn("policy", C.c_int, P, P, P, C.c_int32, P, P, P)
     api["retile32"] = fn("retile32", C.c_int, P, P, P)
+    api["play"] = fn("play", C.c_int, P, P, P, P, P, C.c_int32, P, P, P, C.c_int32, P)
+    api["play_work_floats"] = fn("play_work_floats", C.c_int, C.c_int32)
     api["stats_adam_finish"] = fn("stats_adam_finish", C.c_int, P, P, P, P, P, P, P, C.c_float, P, P, C.c_int32, P, C.c_int32, C.c_int32, C.c_int32, P, P, P)
     api["adam_finish"] = fn("adam_finish", C.c_int, P, P, P, P, P, P, P, C.c_float, P, P, C.c_int32, P, C.c_int32, C.c_int32, C.c_int32, P, P)
     api["finish"] = fn("finish", C.c_int, P, P, C.c_int32, C.c_int32, C.c_int32, P, P)
