@@ -233,7 +233,7 @@ POLICY_COPY_PER_UPDATE = os.environ.get("DW_PPO_POLICY_COPY_PER_UPDATE", "0") ==
 
 def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cfg=None, max_epochs=None, env=None,
           rank=0, world=1, seed=42, graph_rollout=False, graph_update=False, fused_update=False, fused_collective=None, global_gate=False,
-          checkpoint=None, output_dir=None, save_frequency=0, experiment="DyrosDynamicWalk"):
+          checkpoint=None, output_dir=None, save_frequency=0, experiment="DyrosDynamicWalk", episode_stats=False):
     """`epochs` PPO epochs of the DYROS configuration on `num_envs` envs of this rank.  Returns one stats dict per epoch.
     graph_rollout: one rollout step (policy inference, sampling, env step, bookkeeping) is captured once in a hipGraph and
     replayed `horizon` times per epoch -- possible because dw_step_dev keeps the step counter in device memory, so a replayed
@@ -254,7 +254,11 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
     with the schedule's lr and sigma of those epoch numbers, and `frame` continues.  Every rank restores the same file.
     output_dir (rank 0 writes): <output_dir>/<experiment>/nn/<experiment>_<epoch>.pth every save_frequency epochs (0: never) and
     <experiment>.pth after the last epoch.  The reference's last_..._ep_<n>_rew_<r> and best-reward names (a2c_common_dyros.py:1036-1075) need
-    per-episode returns, which this loop does not track; the names here are those of examples/amp_consumer.py."""
+    per-episode returns, which this loop does not track; the names here are those of examples/amp_consumer.py.
+    episode_stats: the env's on-GPU episode statistics (cfg sim.mi355.episode_stats, isaacgymdyros_amd/episode_stats.py; their launch sits inside
+    the captured rollout step like the rest of env.step): every epoch is one window, its summary goes into the epoch's stats dict as
+    "episode_stats" and one more log line gives the termination causes, the three most frequent contact bodies, the mean length and the
+    push falls.  Off: neither the dicts nor the log change."""
     from isaacgymdyros_amd.config import default_cfg
     from isaacgymdyros_amd.dyros_dynamic_walk import DyrosDynamicWalk
     cfg = cfg or TRAIN_CFG
@@ -265,11 +269,16 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
     if own_env:
         ecfg = default_cfg(num_envs, device)
         ecfg["seed"] = seed + rank
+        if episode_stats:
+            ecfg["sim"]["mi355"]["episode_stats"] = True
         if graph_rollout:
             ecfg["sim"]["mi355"]["device_step_counter"] = True
             ecfg["sim"]["mi355"]["alias_obs"] = True          # (the loop copies what it keeps)
         env = DyrosDynamicWalk(ecfg, device, 0, True)
     N = env.num_envs
+    epstats = getattr(env, "episode_stats", None) if episode_stats else None
+    if episode_stats and epstats is None:
+        raise ValueError("episode_stats needs an env built with cfg sim.mi355.episode_stats = True")
     torch.manual_seed(seed)                          # same initial weights on every rank
     net = DyrosActorCritic(env.num_obs, env.num_acts, cfg["network"]).to(device)
     torch.manual_seed(seed + 7919 * rank)            # ... but its own exploration noise (Normal.sample draws from the global generator)
@@ -408,6 +417,8 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
                 g["lr"].fill_(lr)
             else:
                 g["lr"] = lr
+        if epstats is not None:
+            epstats.reset_totals()                                              # (the window is this epoch)
         t0 = time.perf_counter()
         step_time = 0.0
         terms = torch.zeros(len(names) or 15, device=device)
@@ -594,10 +605,15 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
             s.update(play_ms=1e3 * play_time, prep_ms=1e3 * t_prep, update_ms=1e3 * (total - play_time - t_prep))
         frame += H * N
         s["frame"] = frame
+        if epstats is not None:
+            s["episode_stats"] = epstats.summary()
         stats.append(s)
         if rank == 0:
             log("epoch %(epoch)d: fps step %(step_fps).3g  step+inference %(play_fps).3g  total %(total_fps).3g  mean reward %(mean_reward).3f  "
                 "a_loss %(a_loss).3g  c_loss %(c_loss).3g  kl %(kl).2g  lr %(lr).2g  log-sigma %(sigma).3f  episode length %(mean_episode_length).1f" % s)
+            if epstats is not None:
+                from isaacgymdyros_amd.episode_stats import format_line
+                log("epoch %d: %s" % (ep, format_line(s["episode_stats"])))
         if nn_dir and rank == 0 and save_frequency > 0 and ep % save_frequency == 0:
             save(os.path.join(nn_dir, "%s_%d.pth" % (experiment, ep)), ep)
     if nn_dir and rank == 0:
@@ -618,6 +634,7 @@ def main():
     ap.add_argument("--checkpoint", default=None, help="resume from this checkpoint (isaacgymdyros_amd/ppo_checkpoint.py; ours or the reference learner's)")
     ap.add_argument("--output-dir", default=None, help="write checkpoints to <dir>/DyrosDynamicWalk/nn/ (rank 0)")
     ap.add_argument("--save-frequency", type=int, default=None, help="epochs between numbered checkpoints (default: the yaml's 100 with --output-dir)")
+    ap.add_argument("--episode-stats", action="store_true", help="on-GPU termination causes and episode statistics, one log line per epoch")
     a = ap.parse_args()
     save_frequency = a.save_frequency if a.save_frequency is not None else (100 if a.output_dir else 0)
     from isaacgymdyros_amd import dist as dwdist
@@ -625,7 +642,7 @@ def main():
     dev = "cuda:%d" % local_rank
     torch.cuda.set_device(local_rank)
     train(a.num_envs, a.epochs, a.horizon, device=dev, rank=rank, world=world, graph_rollout=a.fused, fused_update=a.fused,
-          checkpoint=a.checkpoint, output_dir=a.output_dir, save_frequency=save_frequency)
+          checkpoint=a.checkpoint, output_dir=a.output_dir, save_frequency=save_frequency, episode_stats=a.episode_stats)
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -30,7 +30,19 @@ def run(args):
     from isaacgymdyros_amd.config import default_cfg
     from isaacgymdyros_amd.dyros_dynamic_walk import DyrosDynamicWalk
     dev = torch.device(args.device)
-    env = DyrosDynamicWalk(default_cfg(args.num_envs, args.device), args.device, 0, True)
+    cfg = default_cfg(args.num_envs, args.device)
+    if args.nominal:
+        # the guide's "nominal environment": no domain randomisation and no pushes.  The encoder noise and biases of the observations have no
+        # switch in the reference, so they stay on
+        cfg["task"]["randomize"] = False
+        cfg["env"]["perturbation"] = False
+        print("nominal environment: task.randomize False, env.perturbation False (encoder noise and biases stay on: the reference has no switch "
+              "for them)", flush=True)
+    if args.episode_length is not None:
+        cfg["env"]["episodeLength"] = float(args.episode_length)
+    if args.report:
+        cfg["sim"]["mi355"]["episode_stats"] = True
+    env = DyrosDynamicWalk(cfg, args.device, 0, True)
     ck = PK.load(args.checkpoint)
     n_obs, n_act = int(ck["model"][PK.PREFIX + "actor_mlp.0.weight"].shape[1]), int(ck["model"][PK.PREFIX + "mu.weight"].shape[0])
     if (n_obs, n_act) != (env.num_obs, env.num_acts):
@@ -61,6 +73,9 @@ def run(args):
             print("reward:", cur_r / k, "steps:", cur_s / k, flush=True)
             if games_played >= args.games:
                 break
+    if args.report:
+        from isaacgymdyros_amd.episode_stats import format_table
+        print(format_table(env.episode_stats.summary()), flush=True)
     env.close()
     if games_played == 0:
         raise SystemExit("no game ended within --max-steps %d" % args.max_steps)
@@ -79,6 +94,9 @@ def main():
     ap.add_argument("--stochastic", action="store_true", help="sample mu + exp(sigma) noise instead of the deterministic mu")
     ap.add_argument("--policy-backend", default="hip", choices=["hip", "torch"])
     ap.add_argument("--export-dir", default=None, help="write the model tensors as the reference's text files here")
+    ap.add_argument("--episode-length", type=float, default=None, help="episode length in seconds (default: the yaml's 32 s)")
+    ap.add_argument("--report", action="store_true", help="collect the on-GPU episode statistics and print their table at the end")
+    ap.add_argument("--nominal", action="store_true", help="task.randomize False and env.perturbation False (encoder noise stays on)")
     ap.add_argument("--device", default="cuda:0")
     run(ap.parse_args())
 

@@ -96,6 +96,13 @@ class DyrosDynamicWalk(VecTask):
         self._bound_obs = self._buf["obs_buf"]
         self._fresh_obs = (not self.alias_obs) and np.isinf(self.clip_obs)
         self.extras["reward_names"] = list(REWARD_NAMES)
+        # cfg sim.mi355.episode_stats: termination causes and per-episode statistics on the device, one launch after every step
+        # (isaacgymdyros_amd/episode_stats.py); off: None, and step() makes no extra launch
+        self.episode_stats = None
+        if self.cfg["sim"].get("mi355", {}).get("episode_stats", False):
+            from .episode_stats import EpisodeStats
+            self.episode_stats = EpisodeStats(self)
+            self.extras["termination_cause"] = self.episode_stats.cause
 
     # ------------------------------------------------------------------ native handle
     def _make_config(self):
@@ -366,6 +373,8 @@ class DyrosDynamicWalk(VecTask):
             log = torch.empty(self.num_envs, self._buf["stacked_rewards"].shape[1] + nc, device=self._tdev, dtype=torch.float)
             _lib.check(self._api, self._api["terrain_log"](self._h, log.data_ptr(), stream))
             self.extras["stacked_rewards"] = log
+        if self.episode_stats is not None:
+            self.episode_stats.record()          # (fills extras["termination_cause"] in place)
         self.obs_dict["obs"] = (self.obs_buf if fresh else self._clip_obs(self.obs_buf)).to(self.rl_device)
         return self.obs_dict, self.rew_buf.to(self.rl_device), self.reset_buf.to(self.rl_device), self.extras
 
@@ -376,6 +385,8 @@ class DyrosDynamicWalk(VecTask):
         nz = noise.data_ptr() if noise is not None else 0
         stream = torch.cuda.current_stream(self._tdev).cuda_stream
         _lib.check(self._api, self._api["reset_idx"](self._h, ids.data_ptr(), int(ids.numel()), nz, self._current_step(), stream))
+        if self.episode_stats is not None:
+            self.episode_stats.restart(ids)          # (the running episodes of these envs are discarded, not counted)
         # (reset_idx does not touch the observations: the reference recomputes them in the next step's post-physics, :655-669)
 
     def _current_step(self) -> int:
@@ -450,6 +461,8 @@ class DyrosDynamicWalk(VecTask):
         self._step_count = int(d["_step_count"])
         if self._step_dev is not None:
             self._step_dev.fill_(self._step_count)
+        if self.episode_stats is not None:
+            self.episode_stats.restart()
 
     def close(self):
         if getattr(self, "_h", None) is not None:
