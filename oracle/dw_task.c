@@ -578,7 +578,9 @@ static int gate_is_open(const DwHandle *h, int64_t step) {
     double n = (double)cfg->num_envs;
     double mean_epi = (double)se / n;
     double mean_crm = (double)sc / 4294967296.0 / n;
-    return mean_epi > (double)(cfg->max_episode_length - 2000.0f) && mean_crm > 0.165;
+    /* 8/self.dt_policy (2000 steps at the YAML's dt only), in the float the kernels carry it in */
+    const float pert_period = (float)(8 / (cfg->dt * cfg->control_freq_inv));
+    return mean_epi > (double)(cfg->max_episode_length - pert_period) && mean_crm > 0.165;
 }
 
 int dwo_step(DwHandle *h, const float *actions, const float *noise, int64_t step_index, void *stream) {

@@ -17,6 +17,11 @@ RNG draws, per-step injected physics state) and the reference's outputs.
                           the fake gym was handed by `set_actor_dof_properties`, plus randomize_buf.  Pins: additive /
                           scaling FROM THE ORIGINAL value, independent per DoF, only for envs with reset_buf set and
                           randomize_buf >= frequency, randomize_buf zeroed for exactly those.
+  task_logic_altcfg.npz   as task_logic_frozen, away from the YAML's defaults: `deathCost` -1.75, `episodeLength` 0.2 s (50 policy
+                          steps, so envs reach max_episode_length - 1 by counting within the 62 recorded steps; one injected
+                          counter as well), `initialHieght` 0.97.  The injected states are calm (upright, no non-foot load)
+                          except where one of the two termination branches is injected on purpose: a non-foot contact
+                          force (collision) or a base tilted by more than 0.5 rad.
   whole_step_oracle.npz   the same class stepping over the ORACLE's physics (the closed PhysX engine cannot
                           be run: physics parity is unpinned).  Pins the orchestration
                           (call order, substep loop, late updates) of dw_step; the HIP library is held to it
@@ -84,6 +89,39 @@ TERRAIN_CASE = dict(mesh_type="heightfield", curriculum=True, num_rows=3, num_co
                     max_init_terrain_level=2, terrain_proportions=[0.3, 0.0, 0.3, 0.2, 0.2])
 
 
+# `env:` keys of the reference's task YAML moved by the "altcfg" fixture, and the DwConfig fields they map to
+ALT_ENV = dict(deathCost=-1.75, episodeLength=0.2, initialHieght=0.97)
+ALT_CALM_ENVS = 3        # envs 0 .. 2 never get a terminating state: they run into the time-out by counting
+
+
+def alt_state(rng2, root, cf, model):
+    """Calms random_state's draw (tilt scaled to a fifth: < 0.14 rad; no load on non-foot bodies), then injects a collision
+    or a tilt of 0.6 .. 0.7 rad into a few envs.  Returns per env 0 = calm, 1 = collision, 2 = orientation."""
+    N = root.shape[0]
+    root[:, 3:6] *= 0.2
+    root[:, 6] = np.sqrt(1.0 - (root[:, 3:6].astype(np.float64) ** 2).sum(axis=1))
+    feet = (model.left_foot_idx, model.right_foot_idx)
+    for b in range(38):
+        if b not in feet:
+            cf[:, b] = 0
+    kind = np.zeros(N, np.int64)
+    for e in range(ALT_CALM_ENVS, N):
+        u = rng2.uniform()
+        if u < 0.04:
+            body = int(rng2.integers(0, 38))
+            if body not in feet:
+                cf[e, body] = rng2.normal(size=3) * 3 + np.array([0, 0, 4.0])
+                kind[e] = 1 if np.linalg.norm(cf[e, body]) > 1.0 else 0
+        elif u < 0.08:
+            ang = rng2.uniform(0.6, 0.7)
+            axis = rng2.normal(size=3)
+            axis /= np.linalg.norm(axis)
+            root[e, 3:6] = axis * np.sin(ang / 2)
+            root[e, 6] = np.cos(ang / 2)
+            kind[e] = 2
+    return kind
+
+
 class DrRecorder:
     """Records the float64 samples `generate_random_samples` hands `apply_random_samples` (python/isaacgym/gymutil.py:
     584-607), in call order, while active."""
@@ -109,22 +147,33 @@ def run(kind: str, N: int, steps: int, seed: int):
     tc = load_task_constants()
     terr = kind == "terrain"
     dr = kind == "dr"
-    frozen = kind == "frozen" or terr or dr
+    alt = kind == "altcfg"
+    frozen = kind == "frozen" or terr or dr or alt
     A = OracleSim(N, task_const=tc, debug_freeze_physics=int(frozen))
-    env, fake, mods = RH.make_reference_env(A, N, seed=seed, terrain=TERRAIN_CASE if terr else None)
+    env, fake, mods = RH.make_reference_env(A, N, seed=seed, terrain=TERRAIN_CASE if terr else None, env=ALT_ENV if alt else None)
     env.randomize = dr        # (other fixtures: off, so that they pin the task logic alone)
     env.reset()
+    alt_cfg = dict(death_cost=float(env.death_cost), max_episode_length=float(env.max_episode_length),
+                   initial_height=float(env.initial_height)) if alt else {}
     B = OracleSim(N, task_const=tc, randomize_dof_on_reset=int(dr), debug_freeze_physics=int(frozen),
-                  terrain=env.terrain if terr else None, **(dict(max_episode_length_s=float(env.max_episode_length_s)) if terr else {}))
+                  terrain=env.terrain if terr else None, **(dict(max_episode_length_s=float(env.max_episode_length_s)) if terr else {}),
+                  **alt_cfg)
     for k in ("mass_scale", "dof_damping", "dof_armature"):
         B.buf[k][:] = A.buf[k]
     if frozen:
         env.perturb_timing[:] = torch.randint(0, 6, (N,))
-        env.progress_buf[0] = 7990
-        env.progress_buf[1] = 7996
+        if alt:
+            # the injected counter (a calm env), already AT max_episode_length - 1: the only way the reference's timeout_buf is
+            # ever set (vec_task.py:325 looks at the counter before post_physics_step resets the env)
+            env.progress_buf[0] = int(env.max_episode_length) - 1
+        else:
+            env.progress_buf[0] = 7990
+            env.progress_buf[1] = 7996
     P.sync_from_reference(env, B.buf)
     init = {k: v.copy() for k, v in B.buf.items()}
     rng = np.random.default_rng(seed)
+    rng2 = np.random.default_rng(seed + 2)
+    alt_count = {"timeout": 0, "collision": 0, "orientation": 0}
     g = torch.Generator().manual_seed(seed + 1)
     rec_steps = {k: [] for k in PER_STEP}
     actions_all, noise_all, inj = [], [], {"root": [], "dof": [], "cf": []}
@@ -137,6 +186,7 @@ def run(kind: str, N: int, steps: int, seed: int):
             env.perturb_start[:, 0] = True
         if frozen:
             root, dof, cf = random_state(rng, N, tc, A.model)
+            alt_kind = alt_state(rng2, root, cf, A.model) if alt else None
             if terr:          # around the tile origin: some robots have "walked" past half a tile, some hardly moved
                 root[:, 0:2] = env.env_origins[:, 0:2].numpy() + rng.normal(size=(N, 2)) * 3
                 root[:, 2] += env.env_origins[:, 2].numpy()
@@ -148,9 +198,17 @@ def run(kind: str, N: int, steps: int, seed: int):
         if bool(env.perturb_start[0, 0]):
             pert_ids = torch.nonzero((env.epi_len % 2000.0) == env.perturb_timing).flatten().numpy()
         rb_before = env.randomize_buf.numpy().copy()
+        prog_before = env.progress_buf.numpy().copy()
         with RH.RngRecorder() as rec, DrRecorder(mods["gymutil"]) as drrec:
             o, r, d, ex = env.step(a.clone())
         reset_ids = d.nonzero().flatten().numpy()
+        if alt:
+            # (check_termination sees the counter after its increment; reset_idx has zeroed it by now)
+            done, timed_out = d.numpy().astype(bool), prog_before + 1 >= env.max_episode_length - 1
+            alt_count["timeout"] += int((done & (alt_kind == 0) & timed_out).sum())
+            alt_count["collision"] += int((done & (alt_kind == 1)).sum())
+            alt_count["orientation"] += int((done & (alt_kind == 2)).sum())
+            assert np.array_equal(done, (alt_kind != 0) | timed_out), t
         nz = P.noise_from_log(rec.log, N, pert_ids, reset_ids, terrain_levels=TERRAIN_CASE["num_rows"] if terr else 0,
                               terrain_curriculum=terr)
         if dr:
@@ -195,7 +253,17 @@ def run(kind: str, N: int, steps: int, seed: int):
     if dr:
         for k, v in dr_steps.items():
             out["step_" + k] = np.stack(v)
-    path = os.path.join(OUT, "dr_reset.npz" if dr else ("terrain_logic_frozen.npz" if terr else ("task_logic_frozen.npz" if frozen else "whole_step_oracle.npz")))
+    if alt:
+        for k, v in alt_cfg.items():
+            out["cfg_" + k] = np.float32(v)
+        sr, rw = out["step_stacked_rewards"], out["step_rew_buf"]
+        dc = np.float32(ALT_ENV["deathCost"])
+        print("altcfg resets by cause:", alt_count, "| stacked_rewards == deathCost:", int((sr == dc).sum()), "| rew_buf == deathCost:", int((rw == dc).sum()))
+        assert alt_count["timeout"] >= 1 + ALT_CALM_ENVS and alt_count["collision"] >= 1 and alt_count["orientation"] >= 1, alt_count
+        assert (sr == dc).any() and (rw == dc).any()
+        assert out["step_timeout_buf"][0, 0] == 1 and out["step_timeout_buf"].sum() == 1
+        assert (out["step_root_states"][:, :, 2] == np.float32(ALT_ENV["initialHieght"])).any()      # a reset env stands at the new height
+    path = os.path.join(OUT, "task_logic_altcfg.npz" if alt else "dr_reset.npz" if dr else ("terrain_logic_frozen.npz" if terr else ("task_logic_frozen.npz" if frozen else "whole_step_oracle.npz")))
     np.savez_compressed(path, **out)
     nres = int(np.stack(rec_steps["reset_buf"]).sum())
     npert = int(np.stack(rec_steps["pert_on"]).sum())
@@ -206,7 +274,7 @@ if __name__ == "__main__":
     warnings.filterwarnings("ignore")
     if not RH.available():
         sys.exit("reference checkout not present; goldens can only be minted where it is mounted")
-    only = sys.argv[1] if len(sys.argv) > 1 else None        # "frozen" | "oracle" | "terrain" | "dr": mint one fixture only
+    only = sys.argv[1] if len(sys.argv) > 1 else None        # "frozen" | "oracle" | "terrain" | "dr" | "altcfg": mint one fixture only
     if only in (None, "frozen"):
         run("frozen", N=24, steps=20, seed=11)
     if only in (None, "oracle"):
@@ -215,3 +283,5 @@ if __name__ == "__main__":
         run("terrain", N=24, steps=24, seed=17)
     if only in (None, "dr"):
         run("dr", N=24, steps=24, seed=23)
+    if only in (None, "altcfg"):
+        run("altcfg", N=8, steps=62, seed=29)

@@ -249,7 +249,8 @@ def load_reference(fake_gym_factory):
     return _loaded
 
 
-def reference_cfg(num_envs: int, randomize: bool = True, perturbation: bool = True):
+def reference_cfg(num_envs: int, randomize: bool = True, perturbation: bool = True, env: dict = None):
+    """The reference's own task YAML; `env`: values for keys of its `env:` section (deathCost, episodeLength, ...)."""
     import yaml
     with open(os.path.join(IGE, "cfg", "task", "DyrosDynamicWalk.yaml")) as f:
         cfg = yaml.safe_load(f)
@@ -260,6 +261,9 @@ def reference_cfg(num_envs: int, randomize: bool = True, perturbation: bool = Tr
     cfg["sim"]["physx"].update(num_threads=4, solver_type=1, use_gpu=False, num_subscenes=4)
     cfg["rl_device"] = "cpu"
     cfg["task"]["randomize"] = randomize
+    for k, v in (env or {}).items():
+        assert k in cfg["env"], k           # an override of a key the reference reads, not a new one
+        cfg["env"][k] = v
     return cfg
 
 
@@ -298,13 +302,13 @@ class RngRecorder:
 
 
 def make_reference_env(osim, num_envs: int, seed: int = 42, randomize: bool = True, perturbation: bool = True,
-                       terrain: dict = None):
+                       terrain: dict = None, env: dict = None):
     """Construct the reference DyrosDynamicWalk on top of `osim` (an oracle.OracleSim with N envs).  `terrain`:
     values for the reference's TerrainCfg class attributes (the reference selects its terrain by editing that class,
-    cfg/terrain/terrain_cfg.py:1-22); they are restored afterwards."""
+    cfg/terrain/terrain_cfg.py:1-22); they are restored afterwards.  `env`: overrides of the YAML's `env:` section."""
     fake = FakeGym(osim)
     mods = load_reference(lambda: fake)
-    cfg = reference_cfg(num_envs, randomize, perturbation)
+    cfg = reference_cfg(num_envs, randomize, perturbation, env)
     torch.manual_seed(seed)
     np.random.seed(seed)
     tcls = sys.modules["isaacgymenvs.cfg.terrain.terrain_cfg"].TerrainCfg

@@ -21,6 +21,10 @@ def make_env(N, **mi):
     seed = mi.pop("seed", None)
     if seed is not None:
         cfg["seed"] = seed
+    # env / sim / physx: overrides of the YAML's own sections (deathCost, episodeLength, dt, gravity, solver iterations, ...)
+    cfg["env"].update(mi.pop("env", {}))
+    cfg["sim"]["physx"].update(mi.pop("physx", {}))
+    cfg["sim"].update(mi.pop("sim", {}))
     cfg["sim"]["mi355"].update(mi)
     return DyrosDynamicWalk(cfg, "cuda:0", 0, True)
 
@@ -45,3 +49,61 @@ class HipBackend:
 
     def read_buffers(self):
         return {k: v.cpu().numpy() for k, v in self.env._buf.items()}
+
+
+class HipSim:
+    """The HIP library behind the same driver as OracleSim / EmulSim, from a DwConfig given field by field (fields the
+    host class pins, max_angular_velocity among them, included): numpy buffers in `buf`, mirrored to device tensors
+    before every call and read back after it."""
+
+    def __init__(self, num_envs, task_const=None, terrain=None, **cfg_over):
+        import ctypes as C
+        from isaacgymdyros_amd import _lib
+        from isaacgymdyros_amd.dyros_dynamic_walk import _TORCH_DT
+        from oracle.oracle import OracleSim
+        # the oracle's driver builds config, model, task constants and initial buffers; only the library differs
+        self._host = OracleSim(num_envs, task_const=task_const, terrain=terrain, **cfg_over)
+        self.cfg, self.N, self.buf = self._host.cfg, num_envs, self._host.buf
+        self.lib, self.api = _lib.load()
+        self._dev = {k: torch.zeros(v.shape, dtype=_TORCH_DT[v.dtype.str[1:]], device="cuda:0") for k, v in self.buf.items()}
+        tptr = C.byref(self._host._task_keep[0]) if self._host._task_keep is not None else None
+        self.h = C.c_void_p()
+        _lib.check(self.api, self.api["create"](C.byref(self.cfg), C.byref(self._host.cmodel), tptr, C.byref(self.h)))
+        db = abi.DwBuffers()
+        for name in abi.BUFFER_NAMES:
+            setattr(db, name, self._dev[name].data_ptr())
+        _lib.check(self.api, self.api["bind"](self.h, C.byref(db)))
+
+    def _up(self):
+        for k, v in self.buf.items():
+            self._dev[k].copy_(torch.from_numpy(v))
+
+    def _down(self):
+        torch.cuda.synchronize()
+        for k, v in self.buf.items():
+            v[...] = self._dev[k].cpu().numpy()
+
+    def simulate(self, tau, push=None):
+        from isaacgymdyros_amd import _lib
+        assert tau.shape == (self.N, 33)
+        self._up()
+        t = torch.from_numpy(np.ascontiguousarray(tau, dtype=np.float32)).cuda()
+        p = None if push is None else torch.from_numpy(np.ascontiguousarray(push, dtype=np.float32)).cuda()
+        _lib.check(self.api, self.api["simulate"](self.h, t.data_ptr(), 0 if p is None else p.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        self._down()
+
+    def step(self, actions, noise=None, step_index=0):
+        from isaacgymdyros_amd import _lib
+        assert actions.shape == (self.N, 13)
+        self._up()
+        a = torch.from_numpy(np.ascontiguousarray(actions, dtype=np.float32)).cuda()
+        nz = None if noise is None else torch.from_numpy(np.ascontiguousarray(noise, dtype=np.float32)).cuda()
+        _lib.check(self.api, self.api["step"](self.h, a.data_ptr(), 0 if nz is None else nz.data_ptr(), step_index, torch.cuda.current_stream().cuda_stream))
+        self._down()
+
+    def close(self):
+        if self.h is not None:
+            torch.cuda.synchronize()
+            self.api["destroy"](self.h)
+            self.h = None
+            self._host = None          # (drops the oracle handle that came with the driver)

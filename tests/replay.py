@@ -40,6 +40,12 @@ def load(name):
     return {k: z[k] for k in z.files}
 
 
+def golden_cfg(g, *names):
+    """DwConfig overrides a fixture records as cfg_<field> (task_logic_altcfg.npz: the values the reference ran with)."""
+    names = names or [k[4:] for k in g if k.startswith("cfg_")]
+    return {k: float(g["cfg_" + k]) for k in names}
+
+
 class OracleBackend:
     def __init__(self, N, task_const, **cfg):
         from oracle.oracle import OracleSim
@@ -59,6 +65,65 @@ class OracleBackend:
 
     def read_buffers(self):
         return self.sim.buf
+
+
+class SimBackend(OracleBackend):
+    """The replay interface over any driver with OracleSim's buf / step (EmulSim, the GPU tests' HipSim)."""
+
+    def __init__(self, sim):
+        self.sim = sim
+
+
+# DwConfig sets of the task logic that the reference has no counterpart for (or that its fixtures do not move), each with the
+# knob it is about: what the set reverts to the default for its baseline run, and the recorded fields that knob must change.
+# max_episode_length = 7993 puts the two counters task_logic_frozen.npz injects (7990, 7996) at the time-out.
+TASK_KNOB_SETS = {
+    "timeout_fix": (dict(timeout_fix=1, death_cost=-1.5, max_episode_length=7993.0, initial_height=0.97),
+                    dict(timeout_fix=0), ["timeout_buf"]),
+    # (root_vel_at_com rides along: the physics alone reads it, so with physics frozen it owns no field here -- the case
+    #  root_vel_at_origin of tests/knob_cases.py holds it)
+    "perturb_off": (dict(perturb=0, root_vel_at_com=0, death_cost=-0.75, max_episode_length=7993.0),
+                    dict(perturb=1), ["pert_on", "perturbation_count", "magnitude"]),
+    "dt": (dict(dt=0.0025, timeout_fix=1, max_episode_length=7993.0, death_cost=-1.5),
+           dict(dt=0.002), ["time", "qvel_noise", "magnitude", "obs_buf"]),
+    "all": (dict(death_cost=-1.5, timeout_fix=1, max_episode_length=7993.0, initial_height=0.97, root_vel_at_com=0, dt=0.0025, perturb=0),
+            dict(death_cost=0.0, timeout_fix=0, max_episode_length=8000.0, initial_height=0.93, root_vel_at_com=1, dt=0.002, perturb=1),
+            ["timeout_buf", "rew_buf", "stacked_rewards", "root_states", "obs_buf", "time", "qvel_noise", "pert_on", "reset_buf"]),
+}
+
+
+def frozen_replay(g, backends, steps=None, recorded_noise=False):
+    """Drives the backends through task_logic_frozen.npz's injected states and actions with in-kernel noise (noise = None) or,
+    `recorded_noise`, the fixture's noise record (an env the fixture's own run did not reset draws zeros at its reset: the
+    same words on every side); yields (t, one snapshot per backend)."""
+    init = {k[5:]: v for k, v in g.items() if k.startswith("init_")}
+    for be in backends:
+        be.load_buffers(init)
+    for t in range(int(g["steps"]) if steps is None else steps):
+        for be in backends:
+            if t == int(g["force_perturb_step"]):          # the population "has learned to walk": pushes start (where perturb = 1)
+                ga = np.array(be.read_buffers()["gate_acc"], copy=True)
+                ga[abi.K["DW_GATE_LATCH"]] = 1
+                be.load_buffers({"gate_acc": ga})
+            be.write_state(g["inj_root"][t], g["inj_dof"][t], g["inj_cf"][t])
+            be.sim.step(g["actions"][t], g["noise"][t] if recorded_noise else None, t)
+        yield (t,) + tuple(P.snapshot_buffers(be.read_buffers()) for be in backends)
+
+
+def frozen_replay_pair(g, a, b, steps=None, recorded_noise=False):
+    return frozen_replay(g, (a, b), steps, recorded_noise)
+
+
+def assert_task_knob_bites(g, task_const, name, recorded, recorded_noise=False):
+    """`recorded`: the oracle's per-step snapshots under TASK_KNOB_SETS[name].  The same replay with the set's knob back at
+    its default differs in every field the knob owns, and the set reaches a time-out."""
+    over, revert, owned = TASK_KNOB_SETS[name]
+    base = OracleBackend(int(g["N"]), task_const, debug_freeze_physics=1, torch_gpu_div=1, **dict(over, **revert))
+    differs = set()
+    for t, sa in frozen_replay(g, (base,), steps=len(recorded), recorded_noise=recorded_noise):
+        differs |= {k for k in owned if not np.array_equal(sa[k], recorded[t][k])}
+    assert differs == set(owned), (name, sorted(set(owned) - differs))
+    assert sum(int(s["timeout_buf"].sum()) for s in recorded) > 0, name
 
 
 def replay(golden, backend, on_step=None):

@@ -1215,3 +1215,152 @@ def test_step_returns_a_fresh_observation_tensor_without_a_copy():
     sd = f_env.state_dict()
     assert torch.equal(sd["obs_buf"], f_env.obs_buf)
     a_env.close(); f_env.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Away from the default configuration: the DwConfig fields no other test moves (tests/knob_cases.py, replay.TASK_KNOB_SETS,
+# tests/golden/task_logic_altcfg.npz)
+import knob_cases as KC
+
+
+@pytest.mark.parametrize("case", list(KC.CASES))
+def test_physics_knobs_vs_oracle(task_const, wave_build, case):
+    """dw_simulate away from the default DwConfig against the oracle, the cases and tolerances of tests/knob_cases.py (each
+    case's knob changes the oracle's own result by >= 20 x the tolerance: test_kernel_emulation.py holds that on the CPU,
+    and it is asserted again here).  One substep: positions 1e-5 against the fp32 oracle; velocities 1e-5 against the fp32
+    oracle where that is met (the contact-free cases must), otherwise against the fp64 oracle within 4 x the fp32-oracle-
+    to-fp64-oracle difference of the scene (one figure per case, the largest over root velocity and qd); forces 1e-3
+    relative on bodies loaded above 50 N, soles on the friction cone 5e-4 / 3e-3 / 1e-2 at the 50th / 99th / 100th
+    percentile.  20 substeps: 1e-4 / 2e-2.
+
+    Measured on the MI355X, worst of the four builds.  Columns: positions after one substep | velocities: kernel vs fp32
+    oracle, kernel vs fp64 oracle, fp32 oracle vs fp64 oracle, bound (4 x the latter) | forces off the cone max, soles on
+    the cone: count, 50th / 99th / 100th | 20 substeps: positions, velocities
+      iters_1                    1.9e-07 | 9.3e-05 5.0e-05  8.5e-05 3.4e-04 | 7.7e-05   12: 1.4e-05 1.1e-04 1.2e-04 | 3.9e-06 1.7e-03
+      iters_12                   1.9e-07 | 9.3e-05 9.1e-05  9.6e-05 3.8e-04 | 7.7e-05   16: 3.3e-05 4.6e-04 4.9e-04 | 1.6e-05 8.1e-04
+      iters_64                   2.8e-07 | 1.4e-04 1.4e-04  5.4e-05 2.2e-04 | 7.7e-05   16: 3.3e-05 3.2e-04 3.5e-04 | 5.8e-06 6.4e-04
+      erp_and_depenetration_cap  4.3e-07 | 2.2e-04 1.7e-04  1.3e-04 5.3e-04 | 6.7e-05    1: 1.3e-05 1.3e-05 1.3e-05 | 8.8e-06 8.1e-04
+      contact_offset             6.0e-07 | 3.0e-04 1.5e-04  1.9e-04 7.8e-04 | 5.5e-05    0                          | 4.1e-05 4.8e-03
+      contact_cfm                1.2e-07 | 5.1e-05 2.9e-05  5.0e-05 2.0e-04 | 1.2e-04    5: 8.5e-06 1.1e-04 1.2e-04 | 2.4e-06 9.7e-04
+      friction_0                 1.2e-07 | 4.8e-05 7.9e-05  7.9e-05 3.2e-04 | 1.6e-04    0                          | 3.9e-06 9.8e-04
+      friction_0.3               1.3e-07 | 6.5e-05 5.1e-05  6.1e-05 2.4e-04 | 1.5e-04   92: 6.4e-06 7.3e-05 8.6e-05 | 1.0e-05 8.7e-04
+      gravity_xy_flight          1.2e-07 | 1.2e-07 1.2e-07  1.2e-07 4.8e-07 | no contact                            | 6.0e-07 5.4e-07
+      gravity_xy_stance          1.9e-07 | 9.4e-05 5.2e-05  9.0e-05 3.6e-04 | 1.6e-04   11: 1.9e-05 2.5e-04 2.7e-04 | 3.2e-06 1.3e-03
+      dt_0.001                   1.2e-07 | 9.8e-05 8.5e-05  7.7e-05 3.1e-04 | 1.3e-04    4: 7.7e-05 8.9e-05 8.9e-05 | 2.0e-06 4.8e-04
+      dt_0.004                   3.3e-07 | 7.9e-05 1.1e-04  5.9e-05 2.4e-04 | 1.2e-04   23: 1.1e-05 3.0e-04 3.3e-04 | 1.0e-05 1.2e-03
+      max_angular_velocity       1.2e-07 | 2.2e-06 1.9e-06  5.1e-07 2.0e-06 | no contact                            | 4.8e-07 1.9e-06
+      root_vel_at_origin         1.2e-07 | 6.0e-07 6.3e-07  4.8e-07 1.9e-06 | no contact                            | 4.2e-07 2.4e-06
+      penalty_ground             8.7e-08 | 4.4e-05 4.0e-05  4.4e-05 1.8e-04 | 4.3e-06    0                          | 1.5e-05 7.4e-04
+      penalty_self_collision     3.0e-08 | 1.7e-06 1.3e-06  1.0e-06 4.2e-06 | 1.5e-05    0                          | 1.8e-07 2.6e-06
+      all_on_terrain             8.0e-07 | 3.2e-04 1.3e-04  2.5e-04 9.9e-04 | 4.0e-05    2: 1.6e-06 2.5e-06 2.5e-06 | 1.8e-05 1.3e-03
+    The four contact-free cases and penalty_self_collision meet 1e-5 as it stands; every case with ground contact takes the
+    fp64 rule.  Closest to its bound: iters_64, 1.4e-4 of 2.2e-4 (qd).  Split by part, its root velocity alone is 1.1e-4 from
+    the fp64 oracle where the two oracles differ by 2.5e-5 -- one env's yaw rate; sweep 63 to sweep 64 still moves that
+    scene's root velocity by 1.1e-4 in the fp64 oracle, so at 64 sweeps the order of the sweeps (block-Jacobi across the feet
+    here) shows as much as the arithmetic does."""
+    from hip_backend import HipSim
+    KC.assert_bites(case, task_const)
+    cfg = dict(KC.case_config(case))
+    sim = HipSim(KC.N_ENVS, task_const=task_const, terrain=cfg.pop("terrain", None), debug_wave_build=wave_build, **cfg)
+    try:
+        one, run = KC.run_case(sim, case)
+    finally:
+        sim.close()
+    KC.check_case(case, one, run, task_const, label="hip wb%d" % wave_build)
+
+
+def test_task_logic_altcfg_vs_reference_golden(task_const, wave_build):
+    """task_logic_altcfg.npz -- the reference class at deathCost -1.75, a 50-step episode (time-outs reached by counting),
+    initialHieght 0.97, injected collision and tilt states -- replayed through the HIP kernels built from the YAML keys:
+    the lists and tolerances of test_task_logic_vs_reference_goldens."""
+    from hip_backend import HipBackend
+    g = R.load("task_logic_altcfg.npz")
+    be = HipBackend(int(g["N"]), randomize=False, debug_freeze_physics=True, torch_gpu_div=False, debug_wave_build=wave_build,
+                    env=dict(deathCost=-1.75, episodeLength=0.2, initialHieght=0.97))
+    c = be.env._ccfg
+    assert {k: float(getattr(c, k)) for k in ("death_cost", "max_episode_length", "initial_height")} == R.golden_cfg(g)
+    for t, ref, got in R.replay(g, be):
+        exact = R.EXACT_LOGIC + ["qpos_noise", "qvel_noise", "root_states", "dof_state"]
+        if "obs_history" in ref:
+            exact = exact + ["action_history", "action_log", "actions_pre", "pre_joint_velocity_states",
+                             "foot_force_pre", "action_torque_pre", "qpos_pre"]
+        bad = P.compare(ref, got, exact=exact, atol=R.TRANSCENDENTAL)
+        assert not bad, (t, bad)
+    assert P.compare(ref, got, atol={"obs_history": (2e-6, 4e-6)}) == []
+
+
+@pytest.mark.parametrize("knobs", list(R.TASK_KNOB_SETS))
+def test_task_knobs_vs_oracle_when_physics_frozen(task_const, wave_build, knobs):
+    """The sets of replay.TASK_KNOB_SETS (timeout_fix, death_cost, max_episode_length, initial_height, root_vel_at_com, dt,
+    perturb off their defaults) through dw_step against the oracle, physics frozen, the fixture's noise record injected: the
+    comparison of test_task_logic_vs_reference_goldens (its exact fields exact, transcendental fields at R.TRANSCENDENTAL).
+    Each set reaches a time-out and changes the fields its knob owns."""
+    from hip_backend import HipSim
+    g = R.load("task_logic_frozen.npz")
+    N = int(g["N"])
+    over = R.TASK_KNOB_SETS[knobs][0]
+    a = R.OracleBackend(N, task_const, debug_freeze_physics=1, torch_gpu_div=1, **over)
+    sim = HipSim(N, task_const=task_const, debug_freeze_physics=1, torch_gpu_div=1, debug_wave_build=wave_build, **over)
+    recorded = []
+    try:
+        for t, sa, sb in R.frozen_replay_pair(g, a, R.SimBackend(sim), recorded_noise=True):
+            exact = R.EXACT_LOGIC + ["qpos_noise", "qvel_noise", "root_states", "dof_state"]
+            bad = P.compare(sa, sb, exact=exact, atol=R.TRANSCENDENTAL)
+            assert not bad, (knobs, t, bad)
+            recorded.append(sa)
+    finally:
+        sim.close()
+    R.assert_task_knob_bites(g, task_const, knobs, recorded, recorded_noise=True)
+
+
+@pytest.mark.parametrize("fix", [False, True])
+def test_time_outs_extra_with_and_without_timeout_fix(fix):
+    """the reference's timeout_buf looks at the counter before post_physics_step advances it and resets
+    the env, so it never reports a time-out; sim.mi355.timeout_fix looks one step ahead.  Through DyrosDynamicWalk.step(): with
+    the fix extras["time_outs"] is exactly the envs that reset because the counter reached max_episode_length - 1, without it
+    zero -- 25-step episodes, so every env times out (or falls) twice in 60 steps."""
+    from hip_backend import make_env
+    N = 64
+    env = make_env(N, randomize=False, timeout_fix=fix, env=dict(episodeLength=0.1))
+    assert env.max_episode_length == 25.0 and env._ccfg.timeout_fix == int(fix)
+    seen = by_count = 0
+    for t in range(60):
+        prog = env.progress_buf.clone()
+        _, _, done, extras = env.step(torch.zeros(N, 13, device="cuda"))
+        at_limit = (prog + 1 >= env.max_episode_length - 1)
+        expect = (done != 0) & at_limit if fix else torch.zeros_like(at_limit)
+        assert torch.equal(extras["time_outs"] != 0, expect), t
+        seen += int((extras["time_outs"] != 0).sum())
+        by_count += int(((done != 0) & at_limit).sum())
+    assert by_count >= N and seen == (by_count if fix else 0)
+    env.close()
+
+
+def test_every_mapped_yaml_field_lands_in_the_config():
+    """YAML -> DwConfig (dyros_dynamic_walk.py::_make_config): every mapped key moved off its default arrives in env._ccfg."""
+    from hip_backend import make_env
+    env = make_env(32, randomize=False,
+                   sim=dict(dt=0.0025, gravity=[0.5, -0.25, -9.0]),
+                   physx=dict(num_position_iterations=7, num_velocity_iterations=2, contact_offset=0.004, max_depenetration_velocity=3.0),
+                   env=dict(deathCost=-1.25, episodeLength=10.0, initialHieght=0.95, perturbation=False),
+                   plane_friction=0.7, erp=0.35, contact_cfm=0.02, penalty_stiffness=5e4, penalty_damping=7e2, timeout_fix=True,
+                   root_vel_at_com=False)
+    c = env._ccfg
+    f32 = lambda x: float(np.float32(x))
+    got = dict(dt=c.dt, gravity=list(c.gravity), solver_iterations=c.solver_iterations, contact_offset=c.contact_offset,
+               max_depenetration_velocity=c.max_depenetration_velocity, death_cost=c.death_cost, max_episode_length=c.max_episode_length,
+               initial_height=c.initial_height, perturb=c.perturb, friction=c.friction, erp=c.erp, contact_cfm=c.contact_cfm,
+               penalty_stiffness=c.penalty_stiffness, penalty_damping=c.penalty_damping, timeout_fix=c.timeout_fix,
+               root_vel_at_com=c.root_vel_at_com, max_angular_velocity=c.max_angular_velocity, control_freq_inv=c.control_freq_inv)
+    want = dict(dt=0.0025, gravity=[0.5, -0.25, -9.0], solver_iterations=9, contact_offset=0.004, max_depenetration_velocity=3.0,
+                death_cost=-1.25, max_episode_length=10.0 / (0.0025 * 2), initial_height=0.95, perturb=0, friction=0.7, erp=0.35,
+                contact_cfm=0.02, penalty_stiffness=5e4, penalty_damping=7e2, timeout_fix=1, root_vel_at_com=0,
+                max_angular_velocity=100.0, control_freq_inv=2)
+    for k, v in want.items():           # (the struct's floats are single precision, dt a double)
+        if isinstance(v, list):
+            assert [f32(x) for x in got[k]] == [f32(x) for x in v], (k, list(got[k]), v)
+        else:
+            assert (got[k] == v) if k == "dt" else (f32(got[k]) == f32(v)), (k, got[k], v)
+    obs, _, _, _ = env.step(torch.zeros(32, 13, device="cuda"))          # and the library accepts the lot
+    assert torch.isfinite(obs["obs"]).all()
+    env.close()

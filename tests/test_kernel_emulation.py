@@ -4,6 +4,7 @@ real library."""
 import numpy as np
 import pytest
 
+import knob_cases as KC
 import replay as R
 from emul_backend import EmulBackend, EmulSim
 from oracle import parity as P
@@ -52,26 +53,45 @@ def test_terrain_curriculum_bitwise_vs_reference_golden(task_const, wave_build):
         assert np.array_equal(g["step_env_origins"][t], got["env_origins"]), t
 
 
-def test_kernel_body_equals_oracle_bitwise_when_physics_frozen(task_const, wave_build):
+@pytest.mark.parametrize("knobs", [None] + list(R.TASK_KNOB_SETS))
+def test_kernel_body_equals_oracle_bitwise_when_physics_frozen(task_const, wave_build, knobs):
     """Same libm on both sides here, so with physics frozen the kernel body and the oracle agree on every bit,
-    in-kernel Philox noise included (noise = None)."""
+    in-kernel Philox noise included (noise = None) -- at the default configuration (None) and at the sets of
+    replay.TASK_KNOB_SETS (timeout_fix, death_cost, max_episode_length, initial_height, root_vel_at_com, dt, perturb off
+    their defaults), each of which reaches a time-out and changes the fields its knob owns."""
     g = R.load("task_logic_frozen.npz")
     N = int(g["N"])
     from replay import OracleBackend
-    a = OracleBackend(N, task_const, debug_freeze_physics=1, torch_gpu_div=1, randomize_friction_on_reset=1)
-    b = EmulBackend(N, task_const, debug_wave_build=wave_build, debug_freeze_physics=1, torch_gpu_div=1, randomize_friction_on_reset=1)
-    init = {k[5:]: v for k, v in g.items() if k.startswith("init_")}
-    a.load_buffers(init)
-    b.load_buffers(init)
-    for t in range(int(g["steps"])):
-        for be in (a, b):
-            be.write_state(g["inj_root"][t], g["inj_dof"][t], g["inj_cf"][t])
-            be.sim.step(g["actions"][t], None, t)
-        sa, sb = P.snapshot_buffers(a.read_buffers()), P.snapshot_buffers(b.read_buffers())
+    over = dict(randomize_friction_on_reset=1) if knobs is None else R.TASK_KNOB_SETS[knobs][0]
+    a = OracleBackend(N, task_const, debug_freeze_physics=1, torch_gpu_div=1, **over)
+    b = EmulBackend(N, task_const, debug_wave_build=wave_build, debug_freeze_physics=1, torch_gpu_div=1, **over)
+    recorded = []
+    for t, sa, sb in R.frozen_replay_pair(g, a, b):
         bad = P.compare(sa, sb, exact=list(sa.keys()))
         assert not bad, (t, bad)
         for k in ("dof_damping", "dof_armature", "friction_scale", "randomize_buf", "gate_acc"):
             assert np.array_equal(a.read_buffers()[k], b.read_buffers()[k]), k
+        recorded.append(sa)
+    if knobs is not None:
+        R.assert_task_knob_bites(g, task_const, knobs, recorded)
+        if "death_cost" in over:
+            assert any((s["rew_buf"] == np.float32(over["death_cost"])).any() for s in recorded)
+
+
+def test_task_logic_altcfg_bitwise_vs_reference_golden(task_const, wave_build):
+    """task_logic_altcfg.npz (the reference class at deathCost -1.75, a 50-step episode, initialHieght 0.97, with time-outs
+    reached by counting) through the kernel source: the lists of test_task_logic_bitwise_vs_reference_goldens."""
+    g = R.load("task_logic_altcfg.npz")
+    be = EmulBackend(int(g["N"]), task_const, debug_wave_build=wave_build, randomize_dof_on_reset=0, debug_freeze_physics=1, torch_gpu_div=0,
+                     **R.golden_cfg(g))
+    for t, ref, got in R.replay(g, be):
+        exact = R.EXACT_LOGIC + ["qpos_noise", "qvel_noise", "root_states", "dof_state"]
+        if "obs_history" in ref:
+            exact = exact + ["action_history", "action_log", "actions_pre", "pre_joint_velocity_states",
+                             "foot_force_pre", "action_torque_pre", "qpos_pre"]
+        bad = P.compare(ref, got, exact=exact, atol=R.TRANSCENDENTAL)
+        assert not bad, (t, bad)
+    assert P.compare(ref, got, atol={"obs_history": (2e-6, 4e-6)}) == []
 
 
 def test_whole_step_tracks_oracle_goldens(task_const, wave_build):
@@ -115,6 +135,33 @@ def test_physics_substep_vs_oracle_random_flight(wave_build):
     assert np.abs(A.buf["root_states"] - B.buf["root_states"]).max() < 1e-4
 
 
+@pytest.mark.parametrize("case", list(KC.CASES))
+def test_physics_knob_bites_in_the_oracle(task_const, case):
+    """The precondition of every case of tests/knob_cases.py, oracle-only arithmetic: the override changes at least one
+    compared quantity by >= 20 x the tolerance that quantity is held to (a kernel that ignored the field could not pass)."""
+    KC.assert_bites(case, task_const)
+    if case.startswith("friction"):
+        KC.check_cone(case, task_const)
+    if case == "erp_and_depenetration_cap":
+        KC.assert_both_cap_branches()
+
+
+@pytest.mark.parametrize("case", list(KC.CASES))
+def test_physics_knobs_vs_oracle(task_const, wave_build, case):
+    """dw_simulate away from the default DwConfig (solver sweeps, erp / depenetration cap, contact margin, cfm, plane
+    friction, tilted gravity, dt, angular-velocity clamp, root velocity convention, penalty constants, and all of them at
+    once on a height field) through the kernel source against the oracle: one substep positions 1e-5, velocities 1e-5 or,
+    with contact, 4 x the fp32-oracle-to-fp64-oracle difference of the scene against the fp64 oracle; forces 1e-3 relative
+    (cone percentiles for sliding soles), 20 substeps 1e-4 / 2e-2 (tests/knob_cases.py).  Measured here, worst case over the
+    table (the three builds give the same numbers): one substep q 7.9e-7; velocities against the fp64 oracle 4.6e-5 .. 2.0e-4
+    with ground contact, where the two oracles differ by 4.4e-5 .. 2.5e-4 (closest to its bound: iters_64, 1.4e-4 of 2.2e-4),
+    <= 2.0e-6 against the fp32 oracle without; forces off the cone 1.6e-4; 20 substeps q 2.9e-5, qd 5.1e-3 (contact_offset)."""
+    cfg = KC.case_config(case)
+    sim = EmulSim(KC.N_ENVS, task_const=task_const, debug_wave_build=wave_build, **cfg)
+    one, run = KC.run_case(sim, case)
+    KC.check_case(case, one, run, task_const, label="emul wb%d" % wave_build)
+
+
 def _gate_roundtrip(make, N=40):
     """Population gate (tasks/dyros_dynamic_walk.py:489): means of epi_len_log and contact_reward_mean over ALL envs
     decide whether pushes start; here via deterministic int64 bucket sums written by step t and read by step t+1."""
@@ -142,6 +189,28 @@ def test_perturbation_gate_latches_identically(task_const, wave_build):
     a = _gate_roundtrip(lambda N: OracleSim(N, task_const=task_const, debug_freeze_physics=1))
     b = _gate_roundtrip(lambda N: EmulSim(N, task_const=task_const, debug_wave_build=wave_build, debug_freeze_physics=1))
     assert np.array_equal(a, b)
+
+
+def _gate_opens(make, epi_len, N=40):
+    from isaacgymdyros_amd import abi
+    sim = make(N)
+    acts = np.zeros((N, 13), np.float32)
+    sim.step(acts, None, 0)
+    abi.es_view(sim.buf["env_state"], "epi_len_log")[:] = epi_len
+    abi.es_view(sim.buf["env_state"], "contact_reward_mean")[:] = 0.18
+    sim.step(acts, None, 1)
+    sim.step(acts, None, 2)
+    return bool(abi.es_view(sim.buf["env_state"], "perturb_start").all()), int(sim.buf["gate_acc"][abi.K["DW_GATE_LATCH"]])
+
+
+@pytest.mark.parametrize("dt,closed_at,open_at", [(0.002, 5900.0, 6100.0), (0.0025, 6300.0, 6500.0), (0.001, 3900.0, 4100.0)])
+def test_perturbation_gate_threshold_follows_dt(task_const, wave_build, dt, closed_at, open_at):
+    """The gate opens when the mean episode length exceeds max_episode_length - 8 / dt_policy (reference :489): 8000 - 2000 at
+    the YAML's dt, 8000 - 1600 at dt = 2.5 ms, 8000 - 4000 at 1 ms.  The oracle had the 2000 as a literal."""
+    for make in (lambda N: OracleSim(N, task_const=task_const, debug_freeze_physics=1, dt=dt),
+                 lambda N: EmulSim(N, task_const=task_const, debug_wave_build=wave_build, debug_freeze_physics=1, dt=dt)):
+        assert _gate_opens(make, closed_at) == (False, 0)
+        assert _gate_opens(make, open_at) == (True, 1)
 
 
 def _crossed(N, symmetric):

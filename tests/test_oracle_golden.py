@@ -25,6 +25,32 @@ def test_task_logic_matches_reference_bitwise(task_const):
     assert P.compare(ref, got, atol={"obs_history": (2e-6, 4e-6)}) == []
 
 
+def test_task_logic_away_from_the_yaml_defaults_matches_reference_bitwise(task_const):
+    """task_logic_altcfg.npz: the reference class with deathCost = -1.75, episodeLength = 0.2 s (50 policy steps: envs time
+    out by counting, and one counter is injected at the limit so that timeout_buf is set once), initialHieght = 0.97 and
+    injected collision / tilt states.  Same exactness lists as the default fixture; the fixture holds every branch."""
+    g = R.load("task_logic_altcfg.npz")
+    cfg = R.golden_cfg(g)
+    assert cfg == {"death_cost": -1.75, "max_episode_length": 50.0, "initial_height": float(np.float32(0.97))}
+    be = R.OracleBackend(int(g["N"]), task_const, randomize_dof_on_reset=0, debug_freeze_physics=1, **cfg)
+    resets = 0
+    for t, ref, got in R.replay(g, be):
+        exact = R.EXACT_LOGIC + ["qpos_noise", "qvel_noise", "root_states", "dof_state"]
+        if "obs_history" in ref:
+            exact = exact + ["action_history", "action_log", "actions_pre", "pre_joint_velocity_states",
+                             "foot_force_pre", "action_torque_pre", "qpos_pre"]
+        bad = P.compare(ref, got, exact=exact, atol=R.TRANSCENDENTAL)
+        assert not bad, (t, bad)
+        resets += int(ref["reset_buf"].sum())
+    assert P.compare(ref, got, atol={"obs_history": (2e-6, 4e-6)}) == []
+    dc = np.float32(-1.75)
+    assert resets >= 30 and g["step_timeout_buf"].sum() == 1
+    assert (g["step_rew_buf"] == dc).sum() >= 30 and (g["step_stacked_rewards"] == dc).any()
+    assert (g["step_root_states"][:, :, 2] == np.float32(0.97)).any()
+    # envs 0 .. 2 are never given a terminating state: they reset when the counter reaches max_episode_length - 1
+    assert g["step_reset_buf"][:, :3].sum() == 4 and g["step_reset_buf"][48, 1] == 1 and g["step_progress_buf"][47, 1] == 48
+
+
 def test_minus_zero_clock_action_survives(task_const):
     """SURVEY a-7: bool*float clamp of the 13th action yields -0.0, which surfaces in obs_buf."""
     g = R.load("task_logic_frozen.npz")

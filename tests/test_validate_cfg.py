@@ -45,6 +45,19 @@ def test_bad_env_and_sim_values_raise():
         validate_cfg(cfg)
 
 
+@pytest.mark.parametrize("pos,vel", [(0, 0), (64, 1), (1, 64)])
+def test_solver_iteration_sum_outside_1_to_64_is_refused(pos, vel):
+    """physx.num_position_iterations + num_velocity_iterations becomes DwConfig.solver_iterations: 0 and 65 are refused, the
+    ends of the range pass."""
+    cfg = default_cfg(64)
+    cfg["sim"]["physx"].update(num_position_iterations=pos, num_velocity_iterations=vel)
+    with pytest.raises(ValueError, match="iterations"):
+        validate_cfg(cfg)
+    for ok in ((1, 0), (63, 1)):
+        cfg["sim"]["physx"].update(num_position_iterations=ok[0], num_velocity_iterations=ok[1])
+        validate_cfg(cfg)
+
+
 def test_constructor_validates_before_touching_the_library(monkeypatch):
     """The task constructor must fail on the cfg check, not on library loading / allocation: make loading the library
     an error and see the ValueError of the cfg instead."""
