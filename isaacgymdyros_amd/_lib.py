@@ -6,13 +6,10 @@ import ctypes as C
 import os
 
 from . import abi
+from .cbind import DyrosWalkLibraryError, check  # noqa: F401  (check(api, rc): raises with the library's last_error())
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libdyroswalk_hip.so")
 _cached = None
-
-
-class DyrosWalkLibraryError(RuntimeError):
-    pass
 
 
 def load():
@@ -35,12 +32,5 @@ def load():
             api = abi.declare(lib, "dw_")
         except AttributeError as e:
             raise DyrosWalkLibraryError("libdyroswalk_hip.so does not export the C-ABI of include/dyros_walk.h: %s" % e)
-        if api["abi_version"]() != abi.K["DW_ABI_VERSION"]:
-            raise DyrosWalkLibraryError("libdyroswalk_hip.so ABI version mismatch; rebuild it")
         _cached = (lib, api)
     return _cached
-
-
-def check(api, rc):
-    if rc != 0:
-        raise DyrosWalkLibraryError("dyroswalk: %s (code %d)" % (api["last_error"]().decode(), rc))

@@ -1,4 +1,4 @@
-"""ctypes mirror of include/dyros_walk.h (structs, constants, function prototypes).
+"""ctypes mirror of include/dyros_walk.h: the structs by hand; the constants and the function prototypes are read from the header (cbind.py).
 
 The reference binds its native engine through pybind11 (`gym_3x.so`) and aliases sim-owned buffers
 with `gymtorch.wrap_tensor` (reference: python/isaacgym/gymtorch.py:61-106).  Here buffers are
@@ -7,25 +7,13 @@ torch-owned and the native side only ever sees raw pointers, so plain ctypes is 
 from __future__ import annotations
 
 import ctypes as C
-import re
 import os
 
+from . import cbind
 from .model import DwModel, DwGeom  # noqa: F401  (re-exported)
 
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dyros_walk.h")
-
-
-def _parse_defines(path):
-    out = {}
-    with open(path) as f:
-        for line in f:
-            m = re.match(r"#define\s+(DW_[A-Z0-9_]+)\s+(-?\d+)\b", line)
-            if m:
-                out[m.group(1)] = int(m.group(2))
-    return out
-
-
-K = _parse_defines(HEADER)          # every integer #define of the header, e.g. K["DW_ES_WORDS"]
+HEADER = os.path.join(cbind.INCLUDE, "dyros_walk.h")
+K = cbind.constants("dyros_walk.h", "dw_")          # every integer #define of the header, e.g. K["DW_ES_WORDS"]
 globals().update(K)
 
 
@@ -128,64 +116,21 @@ class DwAmpResetDraws(C.Structure):         # include/dyros_walk.h: the caller's
     _fields_ = [(n, C.c_void_p) for n in AMP_RESET_DRAW_NAMES]
 
 
+STRUCTS = (DwConfig, DwModel, DwTaskConst, DwBuffers, DwAmpBuffers, DwAmpConfig, DwAmpResetDraws)
+EXPORTS = list(cbind.signatures("dyros_walk.h", "dw_", STRUCTS))
+# The fused TocabiAMPLower step (csrc/dw_amp_step.h) is carried by the HIP library and by the octet build of the host emulation
+# (tests/emul/), its one-launch form and dw_amp_reset_ids by the HIP library alone; the C oracle has neither, nor dw_terrain_log.
+_FUSED_AMP = ("amp_step_begin", "amp_step_mid", "amp_step_end", "amp_step", "amp_reset_rows", "amp_reset_done", "amp_reset_ids")
+MAY_LACK = {"dw_": (),
+            "dwo_": _FUSED_AMP + ("terrain_log",),
+            "dwe_": _FUSED_AMP + ("step_obs", "amp_observations", "amp_disc_observations", "amp_reward", "amp_reset", "newwalk_reward",
+                                  "body_positions")}
+
+
 def declare(lib: C.CDLL, prefix: str = "dw_"):
-    """Attach argtypes/restype for every entry point the header declares; raises AttributeError if the
-    shared object lacks one of them."""
-    def fn(name, restype, *argtypes):
-        f = getattr(lib, prefix + name)
-        f.restype = restype
-        f.argtypes = list(argtypes)
-        return f
-    H = C.c_void_p
-    api = {}
-    api["abi_version"] = fn("abi_version", C.c_int)
-    api["last_error"] = fn("last_error", C.c_char_p)
-    api["default_config"] = fn("default_config", None, C.POINTER(DwConfig))
-    api["create"] = fn("create", C.c_int, C.POINTER(DwConfig), C.POINTER(DwModel), C.POINTER(DwTaskConst),
-                       C.POINTER(H))
-    api["destroy"] = fn("destroy", C.c_int, H)
-    api["bind"] = fn("bind", C.c_int, H, C.POINTER(DwBuffers))
-    api["simulate"] = fn("simulate", C.c_int, H, C.c_void_p, C.c_void_p, C.c_void_p)
-    api["step"] = fn("step", C.c_int, H, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
-    api["step_dev"] = fn("step_dev", C.c_int, H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
-    api["reset_idx"] = fn("reset_idx", C.c_int, H, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p)
-    P = C.c_void_p
-
-    def fused_amp():
-        # the fused TocabiAMPLower step and reset (csrc/dw_amp_step.h)
-        AB, AC = C.POINTER(DwAmpBuffers), C.POINTER(DwAmpConfig)
-        api["amp_step_begin"] = fn("amp_step_begin", C.c_int, H, AC, AB, P, P, P, P)
-        api["amp_step_mid"] = fn("amp_step_mid", C.c_int, H, AC, AB, P, C.c_int, P)
-        api["amp_step_end"] = fn("amp_step_end", C.c_int, H, AC, AB, P, C.c_int, P, P)
-        if prefix == "dw_":          # (the one-launch step lives with the octet kernels' entry points: HIP library only)
-            api["amp_step"] = fn("amp_step", C.c_int, H, AC, AB, P, P, P, C.POINTER(C.c_void_p), C.c_int, P, P)
-            api["amp_reset_ids"] = fn("amp_reset_ids", C.c_int, P, C.c_int, P, P, P, P)
-        api["amp_reset_rows"] = fn("amp_reset_rows", C.c_int, H, AC, AB, P, C.c_int, P, P, P, P, P, P, P, P, P, P)
-        api["amp_reset_done"] = fn("amp_reset_done", C.c_int, H, AC, AB, C.POINTER(DwAmpResetDraws), P)
-
-    if prefix in ("dw_", "dwe_"):
-        api["terrain_log"] = fn("terrain_log", C.c_int, H, C.c_void_p, C.c_void_p)
-    if prefix == "dwe_":        # (the host emulation of the kernels, tests/emul/: the octet library also carries the fused AMP step)
-        if hasattr(lib, "dwe_amp_step_begin"):
-            fused_amp()
-        return api
-    api["step_obs"] = fn("step_obs", C.c_int, H, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
-    # row f-3: env-side functions of the sibling TOCABI tasks (device pointers as c_void_p, trailing stream)
-    api["amp_observations"] = fn("amp_observations", C.c_int, C.c_int, P, P, P, P, P, P, P, P, P)
-    api["amp_disc_observations"] = fn("amp_disc_observations", C.c_int, C.c_int, P, P, P, C.c_int, C.c_int, C.c_int, P, C.c_int, P, P)
-    api["amp_reward"] = fn("amp_reward", C.c_int, C.c_int, P, P, P, P, P, P, P, P, P, P, P, P)
-    api["amp_reset"] = fn("amp_reset", C.c_int, C.c_int, P, P, P, C.c_int, P, P, C.c_float, C.c_int, C.c_float, P, P, P)
-    api["newwalk_reward"] = fn("newwalk_reward", C.c_int, C.c_int, P, P, P, P, P, P, P, C.c_int, P, C.c_int, C.c_float, C.c_float,
-                               C.c_float, P, C.c_int, P, P, P, P, P, P, P, P)
-    api["body_positions"] = fn("body_positions", C.c_int, H, C.POINTER(C.c_int32), C.c_int, P, P)
-    if prefix == "dw_":         # (HIP library; the C oracle does not carry the fused step -- its checkers are the torch class and the emulation)
-        fused_amp()
-    return api
-
-
-EXPORTS = ["abi_version", "last_error", "default_config", "create", "destroy", "bind", "simulate", "step", "step_dev", "step_obs",
-           "terrain_log", "reset_idx", "amp_observations", "amp_disc_observations", "amp_reward", "amp_reset", "newwalk_reward", "body_positions",
-           "amp_step_begin", "amp_step_mid", "amp_step_end", "amp_step", "amp_reset_rows", "amp_reset_done", "amp_reset_ids"]
+    """Every entry point bound with the types its prototype in the header has (cbind); raises AttributeError if the shared object lacks one of
+    them that a library of this prefix has to export, DyrosWalkLibraryError if its ABI version is not the header's."""
+    return cbind.declare(lib, "dyros_walk.h", "dw_", STRUCTS, symbols=prefix, may_lack=MAY_LACK[prefix])
 
 
 # name -> (per-env shape, numpy dtype string); gate_acc is the one buffer without an env dimension

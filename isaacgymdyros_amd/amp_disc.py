@@ -24,24 +24,15 @@ arithmetic with nn.Linear, BCEWithLogitsLoss and autograd.grad(create_graph=True
 from __future__ import annotations
 
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from . import cbind
 
-
-def _constants() -> dict:
-    src = open(os.path.join(ROOT, "include", "dyros_amp_disc.h")).read()
-    return {k: int(v) for k, v in re.findall(r"#define\s+(DWD_[A-Z0-9_]+)\s+(\d+)\b", src)}
-
-
-K = _constants()
+K = cbind.constants("dyros_amp_disc.h", "dwd_")
 HID, OBS_STEP, D_MAX = K["DWD_HID"], K["DWD_OBS_STEP"], K["DWD_D_MAX"]
-EXPORTS = ["abi_version", "last_error", "grad_workspace_bytes", "stats_workspace_bytes", "reward", "stats", "grad", "opt"]
 LOG_NAMES = ["disc_loss", "disc_pred_loss", "disc_logit_loss", "disc_grad_penalty", "disc_weight_decay", "disc_agent_logit", "disc_demo_logit",
              "disc_agent_acc", "disc_demo_acc"]
 DISC_LOGIT_INIT_SCALE = 1.0
@@ -230,22 +221,11 @@ class DwdLoss(C.Structure):          # include/dyros_amp_disc.h
     _fields_ = [("disc_coef", C.c_float), ("logit_reg", C.c_float), ("grad_penalty", C.c_float), ("weight_decay", C.c_float)]
 
 
-def declare(lib: C.CDLL) -> dict:
-    P, I32, I64, F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+EXPORTS = list(cbind.signatures("dyros_amp_disc.h", "dwd_", (DwdLoss,)))
 
-    def fn(name, restype, *argtypes):
-        f = getattr(lib, "dwd_" + name)
-        f.restype, f.argtypes = restype, list(argtypes)
-        return f
-    api = {"abi_version": fn("abi_version", C.c_int), "last_error": fn("last_error", C.c_char_p),
-           "grad_workspace_bytes": fn("grad_workspace_bytes", I64, I32, I32, I32, I32), "stats_workspace_bytes": fn("stats_workspace_bytes", I64, I32),
-           "reward": fn("reward", C.c_int, P, P, P, P, I32, I32, F, F, F, P, P, P, P),
-           "stats": fn("stats", C.c_int, P, I32, I32, P, P, P, P),
-           "grad": fn("grad", C.c_int, P, P, I32, P, I32, P, I32, I32, P, P, P, DwdLoss, P, P, P, I64, P),
-           "opt": fn("opt", C.c_int, P, P, P, P, P, I32, P)}
-    if api["abi_version"]() != K["DWD_ABI_VERSION"]:
-        raise RuntimeError("libdyroswalk_hip.so: dwd ABI %d, include/dyros_amp_disc.h %d: rebuild" % (api["abi_version"](), K["DWD_ABI_VERSION"]))
-    return api
+
+def declare(lib: C.CDLL) -> dict:
+    return cbind.declare(lib, "dyros_amp_disc.h", "dwd_", (DwdLoss,))
 
 
 class AmpDiscriminator:
@@ -314,8 +294,7 @@ class AmpDiscriminator:
         return torch.cuda.current_stream(self.device).cuda_stream
 
     def _check(self, rc):
-        if rc != 0:
-            raise RuntimeError("dwd: %s" % self.api["last_error"]().decode())
+        cbind.check(self.api, rc)
 
     # ------------------------------------------------------------------------------------------------------------- the reward
     def rewards(self, amp_obs: torch.Tensor, task_rewards: torch.Tensor, return_logits: bool = False):

@@ -19,27 +19,16 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
-import re
 
 import torch
 import torch.nn as nn
 
 from . import amp_disc as AD
+from . import cbind
 from .amp_disc import _req
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _constants() -> dict:
-    src = open(os.path.join(ROOT, "include", "dyros_amp_policy.h")).read()
-    return {k: int(v) for k, v in re.findall(r"#define\s+(DWA_[A-Z0-9_]+)\s+(\d+)\b", src)}
-
-
-K = _constants()
+K = cbind.constants("dyros_amp_policy.h", "dwa_")
 HID, D_MAX, A_MAX = K["DWA_HID"], K["DWA_D_MAX"], K["DWA_A_MAX"]
-EXPORTS = ["abi_version", "last_error", "workspace_bytes", "stats_workspace_bytes", "stats", "act", "critic", "grad", "opt", "gae",
-           "play_workspace_bytes", "play"]
 LOG_NAMES = ["a_loss", "c_loss", "b_loss", "clip_frac"]
 
 
@@ -106,42 +95,20 @@ class DwaLoss(C.Structure):          # include/dyros_amp_policy.h
     _fields_ = [("e_clip", C.c_float), ("critic_coef", C.c_float), ("bounds_coef", C.c_float)]
 
 
+EXPORTS = list(cbind.signatures("dyros_amp_policy.h", "dwa_", (DwaLoss,)))
+
+
 def declare(lib: C.CDLL) -> dict:
-    P, I32, I64, F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-
-    def fn(name, restype, *argtypes):
-        f = getattr(lib, "dwa_" + name)
-        f.restype, f.argtypes = restype, list(argtypes)
-        return f
-    api = {"abi_version": fn("abi_version", C.c_int), "last_error": fn("last_error", C.c_char_p),
-           "workspace_bytes": fn("workspace_bytes", I64, I32, I32, I32, I32), "stats_workspace_bytes": fn("stats_workspace_bytes", I64, I32),
-           "stats": fn("stats", C.c_int, P, I32, I32, P, P, P, P),
-           "act": fn("act", C.c_int, P, P, P, P, P, P, I32, I32, I32, P, P, P, P, P, P, I64, P),
-           "critic": fn("critic", C.c_int, P, P, P, P, P, I32, I32, I32, P, P, I64, P),
-           "grad": fn("grad", C.c_int, P, P, P, P, P, P, P, P, I32, I32, I32, DwaLoss, P, P, P, I64, P),
-           "opt": fn("opt", C.c_int, P, P, P, P, P, I32, I32, P),
-           "gae": fn("gae", C.c_int, P, P, P, P, I32, I32, F, F, P, P, P),
-           "play_workspace_bytes": fn("play_workspace_bytes", I64, I32, I32, I32),
-           "play": fn("play", C.c_int, P, P, P, P, P, I32, I32, I32, P, P, P, I64, P)}
-    if api["abi_version"]() != K["DWA_ABI_VERSION"]:
-        raise RuntimeError("libdyroswalk_hip.so: dwa ABI %d, include/dyros_amp_policy.h %d: rebuild" % (api["abi_version"](), K["DWA_ABI_VERSION"]))
-    return api
-
-
-_API = None
+    return cbind.declare(lib, "dyros_amp_policy.h", "dwa_", (DwaLoss,))
 
 
 def _api():
-    global _API
-    if _API is None:
-        from . import _lib
-        _API = declare(_lib.load()[0])
-    return _API
+    from . import _lib
+    return declare(_lib.load()[0])
 
 
 def _check(rc):
-    if rc != 0:
-        raise RuntimeError("dwa: %s" % _api()["last_error"]().decode())
+    cbind.check(_api(), rc)
 
 
 def torch_gae(done, values, rewards, next_values, gamma: float, tau: float):

@@ -1,0 +1,106 @@
+"""ctypes bindings read from the C headers under include/: the header is the one statement of an ABI, and nothing here is kept by hand.
+
+ctypes passes arguments by position and checks nothing, so a prototype that gained a parameter while a hand-written argtypes list kept the
+old one hands a kernel the NEXT argument as its pointer.  Hence: `constants()` reads a header's integer #defines,
+`signatures()` turns every prototype `ret prefix_name(args);` into ctypes classes, `declare()` sets them on a loaded library and compares
+the library's ABI version with the header's.  The headers are written in a narrow style (one declaration per parameter, every parameter
+named, fixed-width scalars); a declaration outside that style raises, it is never guessed.  The struct mirrors stay with their modules.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import re
+
+INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float, "double": C.c_double}
+
+
+class DyrosWalkLibraryError(RuntimeError):
+    pass
+
+
+def _source(header: str) -> str:
+    with open(os.path.join(INCLUDE, header)) as f:
+        return f.read()
+
+
+def constants(header: str, prefix: str) -> dict:
+    """Every integer `#define PREFIX_NAME value` of the header (decimal, negative, 0x); defines with another kind of value are left out."""
+    return {k: int(v, 0) for k, v in re.findall(r"^[ \t]*#define[ \t]+(%s[A-Z0-9_]+)[ \t]+(-?(?:0x[0-9a-fA-F]+|\d+))(?=\s|$)" % prefix.upper(),
+                                                _source(header), re.M)}
+
+
+def _ctype(text: str, structs: dict, named: bool):
+    """The ctypes class of one parameter (named) or return type.  Data pointers stay untyped: the double-precision oracle is bound through
+    the float header, and callers hand over plain addresses, ctypes arrays or byref()."""
+    words = [w for w in re.findall(r"\w+|\S", text) if w != "const"]
+    base, stars = (words[0] if words else ""), (words[1:-1] if named else words[1:])
+    if len(words) >= 1 + named and re.fullmatch(r"[A-Za-z_]\w*", base) and all(s == "*" for s in stars):
+        if stars:
+            if base == "char" and not named:
+                return C.c_char_p
+            return C.POINTER(structs[base]) if base in structs and len(stars) == 1 else C.c_void_p
+        if base in structs:
+            return structs[base]
+        if base in SCALARS:
+            return SCALARS[base]
+        if base == "void" and not named:
+            return None
+    raise TypeError("no ctypes class for %r" % text.strip())
+
+
+_signatures = {}
+
+
+def signatures(header: str, prefix: str, structs=(), source: str = None) -> dict:
+    """name without prefix -> (restype, [argtypes]) of every prototype of the header, in its order.  structs: the ctypes.Structure mirrors
+    that may be passed by value or by pointer, found by their class names.  source: the header's text (tests)."""
+    key = (header, prefix)
+    if source is None and key in _signatures:
+        return _signatures[key]
+    src = re.sub(r"/\*.*?\*/", " ", _source(header) if source is None else source, flags=re.S)
+    by_name, sigs = {s.__name__: s for s in structs}, {}
+    for ret, name, args in re.findall(r"^([\w \t\*]+?)\b%s([a-z_0-9]+)\s*\(([^()]*)\)\s*;" % prefix, src, re.M):
+        args = [] if args.strip() == "void" else args.split(",")
+        try:
+            sigs[name] = (_ctype(ret, by_name, False), [_ctype(a, by_name, True) for a in args])
+        except TypeError as e:
+            raise TypeError("include/%s: %s%s: %s" % (header, prefix, name, e)) from None
+    called = set(re.findall(r"\b%s([a-z_0-9]+)\s*\(" % prefix, src))
+    if called != set(sigs):
+        raise TypeError("include/%s: not read as prototypes: %s" % (header, ", ".join(prefix + n for n in sorted(called ^ set(sigs)))))
+    if source is None:
+        _signatures[key] = sigs
+    return sigs
+
+
+_bound = {}
+
+
+def declare(lib: C.CDLL, header: str, prefix: str, structs=(), symbols: str = None, may_lack=()) -> dict:
+    """name without prefix -> the library's function with restype / argtypes set, for every prototype of the header; bound once per
+    (library, symbol prefix).  symbols: the prefix the library exports the functions under when it is not the header's (the oracle's dwo_,
+    the emulation's dwe_); may_lack: names such a library need not export.  Any other missing symbol is an AttributeError."""
+    symbols = symbols or prefix
+    key = (lib, symbols)
+    if key not in _bound:
+        api = {}
+        for name, (restype, argtypes) in signatures(header, prefix, structs).items():
+            if name in may_lack and not hasattr(lib, symbols + name):
+                continue
+            f = getattr(lib, symbols + name)
+            f.restype, f.argtypes = restype, argtypes
+            api[name] = f
+        want = constants(header, prefix)[prefix.upper() + "ABI_VERSION"]
+        if api["abi_version"]() != want:
+            raise DyrosWalkLibraryError("%s: %sabi_version() is %d, include/%s has %d: rebuild the library"
+                                        % (getattr(lib, "_name", lib), symbols, api["abi_version"](), header, want))
+        _bound[key] = api
+    return _bound[key]
+
+
+def check(api: dict, rc: int):
+    """Every entry point returns 0 or an error code, with the message in its ABI's last_error()."""
+    if rc != 0:
+        raise DyrosWalkLibraryError("%s (code %d)" % (api["last_error"]().decode(), rc))

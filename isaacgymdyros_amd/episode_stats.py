@@ -15,55 +15,22 @@ counted, and the per-env counters restart from progress_buf.
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
-import re
-
 import torch
 
-from . import _lib
+from . import _lib, cbind
+from .cbind import check as _check
 from .ppo_update import _req
 
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dyros_stats.h")
-
-
-def _parse_defines(path):
-    out = {}
-    with open(path) as f:
-        for line in f:
-            m = re.match(r"#define\s+(DWS_[A-Z0-9_]+)\s+(-?(?:0x[0-9a-fA-F]+|\d+))(?:\s|$)", line)
-            if m:
-                out[m.group(1)] = int(m.group(2), 0)
-    out["DWS_SUM_AC"] = out["DWS_CT_WORDS"]                                  # (defined by expression in the header)
-    out["DWS_SUM_WORDS"] = out["DWS_CT_WORDS"] + out["DWS_AC_WORDS"]
-    return out
-
-
-K = _parse_defines(HEADER)
-EXPORTS = ("abi_version", "last_error", "record", "restart", "summarize")
+K = cbind.constants("dyros_stats.h", "dws_")
+K["DWS_SUM_AC"] = K["DWS_CT_WORDS"]                                  # (defined by expression in the header)
+K["DWS_SUM_WORDS"] = K["DWS_CT_WORDS"] + K["DWS_AC_WORDS"]
+EXPORTS = list(cbind.signatures("dyros_stats.h", "dws_"))
 CAUSES = {0: "none", 1: "time_limit", 2: "non_foot_contact", 3: "orientation", 4: "non_finite"}
 CMD_EDGES = (0.0, 0.2, 0.4, 0.6, 0.8)
 
 
-def declare(lib: C.CDLL) -> dict:
-    P, I, F = C.c_void_p, C.c_int32, C.c_float
-
-    def fn(name, restype, *argtypes):
-        f = getattr(lib, "dws_" + name)
-        f.restype, f.argtypes = restype, list(argtypes)
-        return f
-    api = {"abi_version": fn("abi_version", C.c_int), "last_error": fn("last_error", C.c_char_p)}
-    if api["abi_version"]() != K["DWS_ABI_VERSION"]:
-        raise _lib.DyrosWalkLibraryError("libdyroswalk_hip.so: dws ABI %d, header %d: rebuild" % (api["abi_version"](), K["DWS_ABI_VERSION"]))
-    api["record"] = fn("record", C.c_int, I, P, P, P, P, P, P, P, P, P, F, F, P)
-    api["restart"] = fn("restart", C.c_int, I, P, I, P, P, P, P, P)
-    api["summarize"] = fn("summarize", C.c_int, I, P, P, P, P)
-    return api
-
-
-def _check(api, rc):
-    if rc != 0:
-        raise _lib.DyrosWalkLibraryError("dyros_stats: %s (code %d)" % (api["last_error"]().decode(), rc))
+def declare(lib) -> dict:
+    return cbind.declare(lib, "dyros_stats.h", "dws_")
 
 
 def fold(out, num_envs: int, max_episode_length: float, body_names) -> dict:

@@ -27,21 +27,12 @@ are re-pointed at views of the flat fp32 master buffer, so the module used for t
 from __future__ import annotations
 
 import ctypes as C
-import re
-import os
 
 import torch
 
-from . import _lib
+from . import _lib, cbind
 
-
-def _constants() -> dict:
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dyros_ppo.h")).read()
-    return {k: int(v) for k, v in re.findall(r"#define\s+(DWP_[A-Z0-9_]+)\s+(\d+)", src)}
-
-
-K = _constants()
-EXPORTS = ["abi_version", "last_error", "sizeof_mlp", "stage_obs", "bias_relu", "loss", "relu_bwd", "grad_stats", "grad_bucket", "adam", "adam_finish", "stats_adam_finish", "finish", "retile", "mlp", "wgrad", "gae", "rollout_pre", "rollout_post", "policy", "retile32", "play", "play_work_floats"]
+K = cbind.constants("dyros_ppo.h", "dwp_")
 IN, INP, HID, OUTP, ACT = K["DWP_IN"], K["DWP_INP"], K["DWP_HID"], K["DWP_OUTP"], K["DWP_ACT"]
 NW1, NW2, NW3 = 2 * HID * INP, 2 * HID * HID, 2 * OUTP * HID
 NWT = NW1 + NW2 + NW3
@@ -73,39 +64,14 @@ class DwpMlp(C.Structure):          # include/dyros_ppo.h
                                           "x16", "h1", "h2", "out16", "dout16", "dz2", "dz1", "xf", "h1f", "h2f", "doutf", "dz2f", "dz1f")] + [("B", C.c_int32), ("e_clip", C.c_float), ("critic_coef", C.c_float)]
 
 
-def declare(lib: C.CDLL) -> dict:
-    P = C.c_void_p
+EXPORTS = list(cbind.signatures("dyros_ppo.h", "dwp_", (DwpMlp,)))
 
-    def fn(name, restype, *argtypes):
-        f = getattr(lib, "dwp_" + name)
-        f.restype, f.argtypes = restype, list(argtypes)
-        return f
-    api = {"abi_version": fn("abi_version", C.c_int), "last_error": fn("last_error", C.c_char_p), "sizeof_mlp": fn("sizeof_mlp", C.c_int)}
-    if api["sizeof_mlp"]() != C.sizeof(DwpMlp) or api["abi_version"]() != K["DWP_ABI_VERSION"]:
-        raise RuntimeError("libdyroswalk_hip.so and isaacgymdyros_amd/ppo_update.py disagree about include/dyros_ppo.h (DwpMlp is %d bytes here, ABI %d): rebuild"
-                           % (C.sizeof(DwpMlp), K["DWP_ABI_VERSION"]))
-    api["stage_obs"] = fn("stage_obs", C.c_int, P, P, C.c_int32, P, P)
-    api["bias_relu"] = fn("bias_relu", C.c_int, P, P, C.c_int32, P)
-    api["loss"] = fn("loss", C.c_int, P, P, P, P, P, P, P, P, P, P, C.c_int32, C.c_float, C.c_float, P, P)
-    api["relu_bwd"] = fn("relu_bwd", C.c_int, P, P, P, C.c_int32, P)
-    api["grad_stats"] = fn("grad_stats", C.c_int, P, P, P, P, P, P, C.c_int32, P)
-    api["grad_bucket"] = fn("grad_bucket", C.c_int, P, P, P, C.c_float, P)
-    api["adam"] = fn("adam", C.c_int, P, P, P, P, P, P, P, P, C.c_float, P, P, C.c_int32, P, P)
-    api["policy"] = fn("policy", C.c_int, P, P, P, C.c_int32, P, P, P)
-    api["retile32"] = fn("retile32", C.c_int, P, P, P)
-    api["play"] = fn("play", C.c_int, P, P, P, P, P, C.c_int32, P, P, P, C.c_int32, P)
-    api["play_work_floats"] = fn("play_work_floats", C.c_int, C.c_int32)
-    api["stats_adam_finish"] = fn("stats_adam_finish", C.c_int, P, P, P, P, P, P, P, C.c_float, P, P, C.c_int32, P, C.c_int32, C.c_int32, C.c_int32, P, P, P)
-    api["adam_finish"] = fn("adam_finish", C.c_int, P, P, P, P, P, P, P, C.c_float, P, P, C.c_int32, P, C.c_int32, C.c_int32, C.c_int32, P, P)
-    api["finish"] = fn("finish", C.c_int, P, P, C.c_int32, C.c_int32, C.c_int32, P, P)
-    api["retile"] = fn("retile", C.c_int, P, P, P)
-    api["rollout_pre"] = fn("rollout_pre", C.c_int, P, P, P, P, P, P, P, C.c_int32, C.c_int32, P, P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32, P)
-    api["rollout_post"] = fn("rollout_post", C.c_int, P, P, P, P, C.c_int32, P, P, P, C.c_int32, C.c_int32, C.c_float, C.c_float, P, P, C.c_int32, P, P, C.c_int32, P)
-    api["gae"] = fn("gae", C.c_int, P, P, P, P, P, C.c_float, C.c_float, C.c_int32, C.c_int32, P, P)
-    api["mlp"] = fn("mlp", C.c_int, C.POINTER(DwpMlp), P)
-    api["wgrad"] = fn("wgrad", C.c_int, P, P, P, P, P, P, P, P, C.c_int32, P)
-    if api["abi_version"]() != K["DWP_ABI_VERSION"]:
-        raise RuntimeError("libdyroswalk_hip.so: dwp ABI %d, header %d" % (api["abi_version"](), K["DWP_ABI_VERSION"]))
+
+def declare(lib: C.CDLL) -> dict:
+    api = cbind.declare(lib, "dyros_ppo.h", "dwp_", (DwpMlp,))
+    if api["sizeof_mlp"]() != C.sizeof(DwpMlp):
+        raise _lib.DyrosWalkLibraryError("include/dyros_ppo.h: DwpMlp is %d bytes in the library and %d in isaacgymdyros_amd/ppo_update.py: rebuild"
+                                         % (api["sizeof_mlp"](), C.sizeof(DwpMlp)))
     return api
 
 
@@ -120,8 +86,7 @@ def gae(fdones, last_values, mb_fdones, mb_values, mb_rewards, gamma: float, tau
             raise ValueError("gae: expected fp32 GPU tensors of [N] / [N, 1] / [H, N] / [H, N, 1]")
     advs = torch.empty_like(ts[4])
     rc = api["gae"](*[t.data_ptr() for t in ts], float(gamma), float(tau), H, N, advs.data_ptr(), torch.cuda.current_stream(advs.device).cuda_stream)
-    if rc != 0:
-        raise RuntimeError(api["last_error"]().decode())
+    cbind.check(api, rc)
     return advs
 
 
@@ -160,8 +125,7 @@ class RolloutRecorder:
         self.act = torch.empty(self.N, ACT, device=mb["act"].device)
 
     def _chk(self, rc):
-        if rc != 0:
-            raise RuntimeError(self.api["last_error"]().decode())
+        cbind.check(self.api, rc)
 
     def rows(self) -> int:
         """The device row counter, read back (a host sync: call it at the end of an epoch, not per step).  More than H means steps were replayed
@@ -342,8 +306,7 @@ class FusedPpoUpdate:
         return {name: g[o:o + n].view(shape) for name, (o, n, shape) in self._gshape.items()}
 
     def _chk(self, rc):
-        if rc != 0:
-            raise RuntimeError(self.api["last_error"]().decode())
+        cbind.check(self.api, rc)
 
     def policy(self, obs: torch.Tensor, mu: torch.Tensor = None, value: torch.Tensor = None):
         """The rollout's forward in fp32 (dwp_policy): (mu [N, 13], value [N, 1]) for obs [N, 487].  mu / value: output

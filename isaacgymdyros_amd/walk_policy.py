@@ -118,8 +118,7 @@ class WalkPolicy:
         self._chk(self.api["retile32"](self.p.data_ptr(), self.p32f.data_ptr(), s))
 
     def _chk(self, rc):
-        if rc != 0:
-            raise RuntimeError(self.api["last_error"]().decode())
+        _lib.check(self.api, rc)
 
     def work_floats(self, n: int) -> int:
         return int(self.api["play_work_floats"](int(n)))

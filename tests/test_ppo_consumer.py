@@ -235,32 +235,6 @@ def test_operand_order_layouts_are_bijections():
     assert U.K["DWP_P32F_WORDS"] == nw and U.K["DWP_P16F_WORDS"] == nw + 2 * U.HID * U.HID + 2 * U.HID * 32
 
 
-def _c_kinds(args: str):
-    """'const float *p, int32_t B, float x, void *stream' -> ['ptr', 'int', 'float', 'ptr']"""
-    kinds = []
-    for a in [x.strip() for x in args.split(",") if x.strip() and x.strip() != "void"]:
-        kinds.append("ptr" if "*" in a else ("float" if a.split()[0] == "float" else "int"))
-    return kinds
-
-
-def test_ppo_ctypes_prototypes_match_the_header():
-    """ctypes passes arguments by position and checks nothing: a C signature that gained a parameter while the binding kept the old list hands a
-    kernel the NEXT argument as its pointer (the r5m4 memory fault).  Every dwp_* prototype of include/dyros_ppo.h against
-    the argtypes ppo_update.declare() sets: same count, and pointer / int32 / float in the same places."""
-    import ctypes as C
-    import re
-    from isaacgymdyros_amd import build, ppo_update as U
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dyros_ppo.h")).read(), flags=re.S)
-    protos = {m.group(2): (m.group(1).strip(), m.group(3)) for m in re.finditer(r"\b(int|const char \*)\s*(dwp_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", src)}
-    assert sorted(protos) == sorted("dwp_" + n for n in U.EXPORTS)
-    api = U.declare(C.CDLL(build.build()))
-    for name, (ret, args) in protos.items():
-        f = api[name[4:]]
-        got = ["ptr" if (t is C.c_void_p or t is C.c_char_p or hasattr(t, "contents") or issubclass(t, C._Pointer)) else ("float" if t is C.c_float else "int") for t in f.argtypes]
-        assert got == _c_kinds(args), (name, got, _c_kinds(args))
-        assert (f.restype is C.c_char_p) == (ret != "int"), name
-
-
 def test_kernel_pointer_arguments_are_checked_before_a_launch():
     """ppo_update._req: what RolloutRecorder.pre / post, FusedPpoUpdate.policy and bind_batch run on every tensor whose data_ptr() goes to a
     kernel.  A bool mask where the kernel reads int64 would be read 8 x out of bounds: refused on the host, with ValueError."""
