@@ -131,10 +131,7 @@ DW_HD int hist_phys(int head, int logical, int nh) { const int p = head + logica
 // The group's thread count is a parameter of the group type (round 6): 256 for the three step kernels, 128 = the two wavefronts of an octet
 // workgroup for the one-launch step (dw_k_amp_step_oct, dw_oct_kernels.hip), whose 16 envs are the same 16.  Every function below takes the
 // group as a template argument and names its thread count GT.
-#if !defined(DWA_GE)
-#define DWA_GE 16          // (A/B builds only: envs per group of the three step kernels)
-#endif
-constexpr int GT = 256, GE = DWA_GE;
+constexpr int GT = 256, GE = 16;          // (GE: envs per group, the 16 envs of an octet workgroup -- dw_oct_kernels.hip)
 #if defined(__HIPCC__)
 template <int GT_> struct EnvGroupT {
     static constexpr int GT = GT_;
@@ -606,10 +603,7 @@ DW_HD void step_end(const WG &W, GroupLds &S, const dw::DevModel &M, const DwAmp
     // the stacked observation (:540-580): obs slots S (i + 1) - 1, action slots S (i + 1), i < H - 1.  Eight items per thread at a
     // time, every load before the first store (the compiler may not move a load over a store into the same table)
     W.par([&](int t) DWA_INL {
-#if !defined(DWA_SB)
-#define DWA_SB 8          // (A/B builds only)
-#endif
-        constexpr int SB = DWA_SB;          // items per thread in flight (four until round 6)
+        constexpr int SB = 8;          // items per thread in flight (four until round 6)
         for (int i0 = t; i0 < GE * num_obs; i0 += SB * GT) {
             float v[SB];
             size_t dst[SB];

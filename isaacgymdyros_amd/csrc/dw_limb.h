@@ -19,7 +19,7 @@
 namespace dwq {
 
 using dw::DevModel; using dw::PhysParams; using dw::NB; using dw::ND;
-using dw::cross3; using dw::dot3; using dw::m3v; using dw::m3tv; using dw::dot6; using dw::quat_to_mat; using dw::sym6;
+using dw::cross3; using dw::dot3; using dw::m3v; using dw::m3tv; using dw::quat_to_mat; using dw::sym6;
 
 #if defined(__HIPCC__)
 typedef float4 F4;
@@ -46,7 +46,7 @@ DQ_HD int f2i(float f) { return __builtin_bit_cast(int, f); }
 // and instruction -- at 5.6 cycles per SIMD where two plain instructions take 9.3 (tools/valu_issue.hip), and the step kernel is bound by
 // vector issue.  The SLP vectoriser forms such pairs from scalar code at the price of moves and registers (612 B of
 // scratch); written as 2-vectors the pairs are the data's own layout -- a 6-vector is (v0 v1)(v2 v3)(v4 v5), a slot row's .xy / .zw are
-// pairs as they come from LDS -- and a scalar factor is the instruction's op_sel broadcast: no moves.  dot6 is then 3 packed + 1 add
+// pairs as they come from LDS -- and a scalar factor is the instruction's op_sel broadcast: no moves.  A dot product (v6_dot) is then 3 packed + 1 add
 // (instead of 6), a scaled add 3 (instead of 6).  Summation order of a dot product: (0, 2, 4) and (1, 3, 5) side by side, then their sum.
 // OQ_PACKED (set by the translation unit): 1 = the pairs are 2-vectors and compile to the packed instructions -- the hex instantiation
 // (dw_hex_kernels.hip), whose lone wave per SIMD issues a packed instruction in 6.1 cycles against 11.0 for two plain ones: -1.9 % of the

@@ -36,7 +36,7 @@ namespace OCT_NS {
 
 using namespace dw;       // DevModel, PhysParams, small vector helpers
 using dwq::F4; using dwq::mk4; using dwq::P2; using dwq::V6; using dwq::v6; using dwq::v6_zero; using dwq::v6_from; using dwq::v6_to; using dwq::v6_dot; using dwq::v6_axpy; using dwq::v6_scale; using dwq::v6_add; using dwq::ld4; using dwq::f2i; using dwq::QHot; using dwq::QuadModel; using dwq::QInRec;
-using dwq::lane_id; using dwq::quad_bcast; using dwq::quad_xor1; using dwq::quad_xor2; using dwq::quad_xor1_hi; using dwq::oct_fetch; using dwq::half_bits_to_float; using dwq::quad_pair_lo; using dwq::quad_pair_hi; using dwq::oct_xor4; using dwq::oct_lo; using dwq::oct_hi; using dwq::oct_take_lo; using dwq::oct_take_hi; using dwq::rs_take; using dwq::rs_all; using dwq::hex_xor8; using dwq::quarter_take; using dwq::quarter0_all; using dwq::wave_any; using dwq::wave_ballot;
+using dwq::lane_id; using dwq::quad_bcast; using dwq::quad_xor1; using dwq::quad_xor2; using dwq::quad_xor1_hi; using dwq::oct_fetch; using dwq::half_bits_to_float; using dwq::quad_pair_lo; using dwq::quad_pair_hi; using dwq::oct_xor4; using dwq::oct_lo; using dwq::oct_hi; using dwq::rs_take; using dwq::rs_all; using dwq::hex_xor8; using dwq::wave_any; using dwq::wave_ballot;
 using dwq::wave_sync; using dwq::wave_sync_global; using dwq::atomic_add_u64; using dwq::rcp_fast; using dwq::sincos_fast; using dwq::qmul; using dwq::quad_bcast_arr; using dwq::quad_take_arr; using dwq::over_1n;
 using dwq::geom_force; using dwq::rigid_inertia; using dwq::rigid_inertia_pre; using dwq::add_rigid; using dwq::seg_seg; using dwq::seg_dist2_fast; using dwq::capsule_pair;
 using dwq::QS_MAX; using dwq::QMAX_OWN; using dwq::QMAX_GYM; using dwq::QMAX_GEOM;
@@ -45,11 +45,7 @@ using dwq::QS_MAX; using dwq::QMAX_OWN; using dwq::QMAX_GYM; using dwq::QMAX_GEO
 // compiler turns into the scalar-base + 32-bit vector-offset form of the global instructions (no 64-bit address arithmetic in the
 // vector pipe: 522 such instructions in the listing of round 4).  The largest stream is obs_history, 2 960 B per env (obs_buf: 1 948 B): the
 // byte offset fits 32 bits up to 1.45 M envs per GPU; config.validate_cfg / dw_create refuse more than 2^20.
-#if defined(OQ_IX64)
-using OQ_IX = size_t;
-#else
 using OQ_IX = unsigned int;
-#endif
 // element i of a stream: the BYTE offset is formed in 32 bits and added to the (wave-uniform) base, which is what selects the
 // scalar-base form `global_load v, v_offset, s[base:base+1]`; indexing a pointer with a 32-bit integer does not (the scaling by the
 // element size is done after the extension to 64 bits: v_lshl_add_u64 / v_mad_u64_u32, the latter at a quarter of the issue rate)
@@ -85,25 +81,17 @@ DQ_HD OQ_IX oq_row(int stride, int env) { return ((OQ_IX)stride & 0xffffffu) * (
 constexpr int LPE = OCT_LPE;         // lanes per env
 constexpr int EPO = 64 / LPE;        // envs per wavefront
 constexpr int NQ = LPE / 4;          // quads ("halves" / quarters) of an env
-#if !defined(OCT_WPG)
-#define OCT_WPG 2
-#endif
-constexpr int WPG = OCT_WPG;         // wavefronts per workgroup (they share the hot tables, nothing else)
+constexpr int WPG = 2;               // wavefronts per workgroup (they share the hot tables, nothing else)
 // The articulated recursion of the inward pass with its spatial ROWS split between the two halves of a limb (octet layout; round 6):
 // half 0 keeps the angular rows of IA / pA, half 1 the linear rows (dw_oct.h "inward pass").  In the hex instantiation quarters 0 and 1 of an env
-// are that pair (quarters 2 and 3 run the same instructions on values nobody reads); -DOCT_NO_ROWSPLIT builds the mirrored form of round 5.
-#if !defined(OCT_NO_ROWSPLIT)
-#define OQ_ROWSPLIT 1
-#else
-#define OQ_ROWSPLIT 0
-#endif
+// are that pair (quarters 2 and 3 run the same instructions on values nobody reads).
 constexpr int SC_PARK_WORDS = QMAX_OWN * 6 + 2;      // per lane: PhysParams::sc_park (the wrenches of up to QMAX_OWN own proxies, their Gym bodies one byte each)
 static_assert(QMAX_OWN <= 8, "the Gym bodies of a lane's own proxies travel in two words, one byte each");
 
 // One wave's body slots: slot[body * 4 + row][position], 64 bytes per body and env.  A row is 8 envs x 16 B
 // = 128 B, half the width of the LDS (64 banks x 4 B); the position code (pcode_cell below) rotates a limb's column by two per limb,
-// so the four limbs of a 16-lane group (2 envs) read 8 different 16-byte columns (`flip`, a pairwise swap of the rows of odd limbs, is
-// what round 3's code did instead and survives for the A/B builds).
+// so the four limbs of a 16-lane group (2 envs) read 8 different 16-byte columns (round 3's code also swapped the rows of odd limbs
+// pairwise; this one needs no row swap, so a limb's position code is ONE byte offset).
 constexpr int XROWS = LPE == 16 ? 12 : 0;          // (hex: the post phase's LDS image needs 124 words more than 33 bodies x 4 envs give)
 constexpr int ROWB = EPO * 16;                      // bytes of a slot row
 struct alignas(16) OSlots { F4 slot[NB * 4 + XROWS][EPO]; };
@@ -112,28 +100,20 @@ struct alignas(16) OLds {
     QHot   hot;
 };
 static_assert(sizeof(OLds) * (8 / WPG) <= 163840, "OLds: 8 waves per CU must fit 160 KB of LDS");
-// (as byte offsets: even rows of a flipped limb lie one row up, odd rows one row down -- two lane-dependent bases, so that every
-//  access is base + a compile-time offset and the compiler need not keep one address register per body and row)
+// (a position code is a byte offset: every access is lane base + a compile-time offset, and the compiler need not keep one address
+//  register per body and row)
 // A body's slot is its CELL: cellbase[owner lane] + outward step (dw_quad_model.h), so a limb's bodies lie in schedule order and
 // the chain passes, unrolled over the steps, address them as lane base + compile-time offset: no slot address depends on a
 // table read.  OQ_SLOT(st, q, p): row q of the body that the limb of position code p visits in outward step st; item lanes
 // and cross-limb reads reach a body through icode() (cell from the owner table) with st = 0.
-struct OPos { int e, o; };
+struct OPos { int off; };
 DQ_HD OPos pcode_cell(int el, int owner, int cell) {
-    // Which column (and, with `flip`, which row of a pair) a limb of env `el` uses.  A/B of four codes on one box with the LDS counters
+    // Which column a limb of env `el` uses: rotated by two per limb.  A/B of four codes on one box with the LDS counters
     // (profiles/r04_lds_position_code_ab.txt): every limb in column el ("naive") has 2.6 x the bank-conflict cycles and costs 1.5 % of
-    // the step; the three rotations below differ by at most 21 % in conflict cycles and the shipped one is the fastest by 0.5 % (16384
-    // envs) and 0.9 % (4096 envs) -- it needs no row swap, so both row bases of a limb are one register.
-#if defined(OCT_PCODE_NAIVE)          // (A/B builds only)
-    const int pos = el & 7, flip = 0;
-#elif defined(OCT_PCODE_R3)           // (A/B builds only: the code of round 3 -- arms four columns from the legs, rows of odd limbs swapped pairwise)
-    const int pos = (el + 4 * (owner >> 1)) & 7, flip = owner & 1;
-#elif defined(OCT_PCODE_ROT1F)        // (A/B builds only: columns rotated by one per limb, rows of odd limbs swapped)
-    const int pos = (el + owner) & 7, flip = owner & 1;
-#else                                 // columns rotated by two per limb, no row swap
-    const int pos = LPE == 8 ? ((el + 2 * owner) & 7) : ((el + owner) & 3), flip = 0;
-#endif
-    OPos p; p.e = cell * (4 * ROWB) + pos * 16 + flip * ROWB; p.o = cell * (4 * ROWB) + pos * 16 - flip * ROWB;
+    // the step; three rotations differ by at most 21 % in conflict cycles and this one is the fastest by 0.5 % (16384 envs) and
+    // 0.9 % (4096 envs).
+    const int pos = LPE == 8 ? ((el + 2 * owner) & 7) : ((el + owner) & 3);
+    OPos p; p.off = cell * (4 * ROWB) + pos * 16;
     return p;
 }
 DQ_HD OPos pcode(const QHot &H, int el, int owner) {          // a limb: cell = cellbase + step
@@ -148,7 +128,7 @@ DQ_HD OPos icode(const QHot &H, int el, int b) {              // a body
 //   row 0 {S0 S1 S2 S3}   row 1 {S4 S5 1/D u}   row 2 {U0 U1 U2 U3}   row 3 {U4 U5 qd *}
 // (S = joint axis as a spatial vector, angular part first; U = IA S).  Outward pass 2 puts the free joint velocity over qd and clears u, the
 // impulse up-sweep puts its d where u was, the final pass leaves row 0 = {q_lo, qd_new, q_hi, *} for the integration.
-#define OQ_SLOT(st, q, p) (*reinterpret_cast<F4 *>(reinterpret_cast<char *>(&L.slot[0][0]) + (((q) & 1) ? (p).o : (p).e) + ((st) * 4 + (q)) * ROWB))
+#define OQ_SLOT(st, q, p) (*reinterpret_cast<F4 *>(reinterpret_cast<char *>(&L.slot[0][0]) + (p).off + ((st) * 4 + (q)) * ROWB))
 #define OQ_LD(b, q, p) ldp(OQ_SLOT(b, q, p))
 #define OQ_S6(r0, r1) v6((r0).x, (r0).y, (r0).z, (r0).w, (r1).x, (r1).y)          // S from rows 0, 1 / U from rows 2, 3
 // the loops over the schedule steps stay loops: unrolled, one substep is 100 KB of straight-line code that every wave streams
@@ -157,7 +137,7 @@ DQ_HD OPos icode(const QHot &H, int el, int b) {              // a body
 #define DQ_PRAGMA_(x) _Pragma(#x)
 #define DQ_PRAGMA(x) DQ_PRAGMA_(x)
 #define DQ_ROLLED DQ_PRAGMA(clang loop unroll_count(OCT_CHAIN_UNROLL))
-#elif defined(__HIPCC__) && !defined(OCT_UNROLLED)
+#elif defined(__HIPCC__)
 #define DQ_ROLLED _Pragma("clang loop unroll(disable)")
 #else
 #define DQ_ROLLED
@@ -210,16 +190,7 @@ struct OLane {
     int   stamp_base;                        // profiling builds only
 };
 
-// add_rigid of dw_limb.h in two parts: IA += rigid inertia [[Ao, H], [H', m 1]], H = skew(ho) ...
-DQ_HD void add_rigid_inertia(float *IA, const float *Ao, const float *ho, float mass) {
-    DQ_UNROLL for (int r = 0; r < 3; ++r)
-        DQ_UNROLL for (int c = r; c < 3; ++c) IA[sym6(r, c)] += dwq::ao(Ao, r, c);
-    IA[sym6(0, 4)] += -ho[2]; IA[sym6(0, 5)] += ho[1];
-    IA[sym6(1, 3)] += ho[2];  IA[sym6(1, 5)] += -ho[0];
-    IA[sym6(2, 3)] += -ho[1]; IA[sym6(2, 4)] += ho[0];
-    IA[sym6(3, 3)] += mass; IA[sym6(4, 4)] += mass; IA[sym6(5, 5)] += mass;
-}
-// ... and the gyroscopic bias pv = v x* (I v)
+// the gyroscopic bias pv = v x* (I v) of a rigid inertia [[Ao, H], [H', m 1]], H = skew(ho) (the second part of dw_limb.h's add_rigid)
 DQ_HD void rigid_bias(const float *Ao, const float *ho, float mass, const float *v, float *pv) {
     const float *om = v, *vl = v + 3;
     float n[3], f[3], t1[3], t2[3];
@@ -397,11 +368,7 @@ DQ_HD void oct_substep(OSlots &L, const QHot &H, const QuadModel &QM, const DevM
         p0w[0] = x4.x + t0[0]; p0w[1] = x4.y + t0[1]; p0w[2] = x4.z + t0[2];
         p1w[0] = x4.x + t1[0]; p1w[1] = x4.y + t1[1]; p1w[2] = x4.z + t1[2];
     };
-#if defined(OCT_ABL_SC)
-    if (false) {
-#else
     if (P.self_collision && npair > 0) {
-#endif
         DQ_STAMP(B, 51);
         unsigned long long hits = 0ull;          // bit k: pair k may touch (up to DW_MAX_SC_PAIRS = 64 pairs)
         {
@@ -509,28 +476,20 @@ DQ_HD void oct_substep(OSlots &L, const QHot &H, const QuadModel &QM, const DevM
     //      contributes by itself -- joint subspace, rigid inertia about O, gyroscopic bias, external forces, velocity-product
     //      acceleration: more than half of a step's arithmetic, and no recursion in it -- is a MAP over bodies: half 0 of a limb
     //      maps the body of step 2 r, half 1 the body of step 2 r + 1, at the same time.  The recursion proper (add into the
-    //      running inertia, U = IA S, rank-1 downdate, bias) then runs for step 2 r on half 0's result, takes half 1's result
-    //      over (31 words, one DPP move each) and runs for step 2 r + 1.  Half 1 executes the recursion's instructions on
-    //      values nobody reads (its stores are masked); it gets the base's inertia back before the base solve. ----
-#if OQ_ROWSPLIT
-    //      ROW SPLIT (octet layout, round 6).  The recursion itself is sequential along the limb, so until round 5 half 1 repeated half
-    //      0's instructions on dead values.  Now the two halves of a limb hold different ROWS of every spatial quantity: half 0 the
+    //      running inertia, U = IA S, rank-1 downdate, bias) then runs for step 2 r on half 0's map and for step 2 r + 1 on half 1's. ----
+    //      ROW SPLIT (round 6).  The recursion itself is sequential along the limb (until round 5 half 1 repeated half 0's
+    //      instructions on dead values), so the two halves of a limb hold different ROWS of every spatial quantity: half 0 the
     //      angular rows of IA = [[A, H], [H', M]] and of pA, half 1 the linear rows.  Stored alike in both: Dm = the symmetric diagonal
     //      block of my rows (A | M, 6 words), Om = their off-diagonal block (H | H', 9 words), pO = my three rows of pA; of a
     //      6-vector x a lane uses own(x) = its three rows and oth(x) = the other three.  Then U_own = Dm own(S) + Om oth(S) is 18
     //      products per lane instead of 36, the rank-1 downdate 15 instead of 21, IA c 18 instead of 36; D = S'U and u = tt - S'pA are
     //      sums over the pair (oct_xor4), and U's other three rows come across the same way.  The map of a step is made by one half
-    //      and handed to BOTH in own / oth form (oct_take_lo / _hi: one bank-masked move per word, the making half keeps its own).
+    //      and handed to BOTH in own / oth form (rs_take: one bank-masked move per word, the making half keeps its own).
     float Dm[6], Om[9], pO[3];
     DQ_UNROLL for (int i = 0; i < 6; ++i) Dm[i] = 0.0f;
     DQ_UNROLL for (int i = 0; i < 9; ++i) Om[i] = 0.0f;
     DQ_UNROLL for (int i = 0; i < 3; ++i) pO[i] = 0.0f;
     const float hsgn = (X.q & 1) ? -1.0f : 1.0f;          // my off-diagonal block of a rigid inertia is skew(ho) (half 0) or its transpose (half 1)
-#else
-    float IA[21], pA[6];          // running reflected inertia / bias (no lane parks a second one: build_quadmodel(accumulate))
-    DQ_UNROLL for (int i = 0; i < 21; ++i) IA[i] = 0.0f;
-    DQ_UNROLL for (int i = 0; i < 6; ++i) pA[i] = 0.0f;
-#endif
     X.footF[0] = X.footF[1] = X.footF[2] = 0.0f;
     const int my_sole_gym = (j == 0) ? M.left_foot_gym : (j == 1 ? M.right_foot_gym : -1);
     struct BodyMap { float Ao[6], ho[3], mass, pv[6], S[6], cb[6], tt, dd, qd; };       // 31 words
@@ -545,11 +504,7 @@ DQ_HD void oct_substep(OSlots &L, const QHot &H, const QuadModel &QM, const DevM
 #define OQ_TICK() ((void)0)
 #define OQ_TOCK(acc) ((void)0)
 #endif
-#if defined(OCT_ABL_INWARD)
-    DQ_ROLLED for (int s = 0; s < 0; s += 2) {
-#else
     DQ_ROLLED for (int s = 0; s < T; s += NQ) {          /*@trip:6*/
-#endif
         OQ_TICK();
 #if defined(DQ_STAMPS_INWARD)
         if (SB == 1) DQ_STAMP(B, 42 + s);
@@ -601,9 +556,6 @@ DQ_HD void oct_substep(OSlots &L, const QHot &H, const QuadModel &QM, const DevM
                 DQ_UNROLL for (int t = 0; t < QMAX_GYM; ++t) cf[t][0] = cf[t][1] = cf[t][2] = 0.0f;
                 bool near_ground = ngeom > 0 && (X.root[2] + x[2] < h0.w);
                 if (TERRAIN) near_ground = ngeom > 0 && (X.root[2] + x[2] - X.zbound < h0.w);
-#if defined(DQ_KO_GEOM) || defined(OCT_ABL_GEOM)          // (timing experiment only)
-                near_ground = false;
-#endif
                 if (near_ground) {          /*@prob:0.17*/
                     const QInRec &rc = QM.in[sm][j];
                     for (int k = 0; k < ngeom; ++k) {
@@ -649,7 +601,6 @@ DQ_HD void oct_substep(OSlots &L, const QHot &H, const QuadModel &QM, const DevM
         }
         wave_sync();          // every map has read its slot rows before the recursion overwrites any
         OQ_TOCK(tq_map); OQ_TICK();
-#if OQ_ROWSPLIT
         // ---- recursion: step s + t2 on the map quarter t2 made, rows split over the working pair ----
         DQ_UNROLL for (int t2 = 0; t2 < NQ; ++t2) {
             const int sr = s + t2;
@@ -758,99 +709,6 @@ DQ_HD void oct_substep(OSlots &L, const QHot &H, const QuadModel &QM, const DevM
                 }
             }
         }
-#else
-        // ---- recursion: step s on half 0's map, then step s + 1 on half 1's ----
-        BodyMap Mq = Mb;          // (hex layout: quad 0 takes the maps of quads 1, 2, 3 in turn from the lanes that made them)
-        DQ_UNROLL for (int t2 = 0; t2 < NQ; ++t2) {
-            const int sr = s + t2;
-            if (sr >= T) break;
-            if (LPE == 8 && t2 == 1) {        // half 1's map result to half 0 (the high quads keep their own)
-                DQ_UNROLL for (int i = 0; i < 6; ++i) { Mb.Ao[i] = oct_hi(Mb.Ao[i]); Mb.pv[i] = oct_hi(Mb.pv[i]); Mb.S[i] = oct_hi(Mb.S[i]); Mb.cb[i] = oct_hi(Mb.cb[i]); }
-                DQ_UNROLL for (int i = 0; i < 3; ++i) Mb.ho[i] = oct_hi(Mb.ho[i]);
-                Mb.mass = oct_hi(Mb.mass); Mb.tt = oct_hi(Mb.tt); Mb.dd = oct_hi(Mb.dd); Mb.qd = oct_hi(Mb.qd);
-            }
-            if (LPE == 16 && t2 >= 1) {
-                auto take = [&](float x) { return t2 == 1 ? quarter_take<1>(x) : (t2 == 2 ? quarter_take<2>(x) : quarter_take<3>(x)); };
-                DQ_UNROLL for (int i = 0; i < 6; ++i) { Mb.Ao[i] = take(Mq.Ao[i]); Mb.pv[i] = take(Mq.pv[i]); Mb.S[i] = take(Mq.S[i]); Mb.cb[i] = take(Mq.cb[i]); }
-                DQ_UNROLL for (int i = 0; i < 3; ++i) Mb.ho[i] = take(Mq.ho[i]);
-                Mb.mass = take(Mq.mass); Mb.tt = take(Mq.tt); Mb.dd = take(Mq.dd); Mb.qd = take(Mq.qd);
-            }
-            const int bits = f2i(H.in[sr][j][0]);
-            const int b = (bits & 255) - 1;
-            const int flags = b >= 0 ? ((bits >> 8) & 7) : 0;
-            const int gw = H.gany[sr];
-            if (gw >> 8) {  /*@prob:0.09*/      // a finished chain joins the finished chain of an idle lane (same parent) before its lane starts afresh
-                const int src = (gw >> 9) & 3, dst = (gw >> 11) & 3;
-                float tI[21], tp[6];
-                quad_bcast_arr(src, IA, tI);
-                quad_bcast_arr(src, pA, tp);
-                if (j == dst) {
-                    DQ_UNROLL for (int i = 0; i < 21; ++i) IA[i] += tI[i];
-                    DQ_UNROLL for (int i = 0; i < 6; ++i) pA[i] += tp[i];
-                }
-            }
-            if (flags & 1) {
-                DQ_UNROLL for (int i = 0; i < 21; ++i) IA[i] = 0.0f;
-                DQ_UNROLL for (int i = 0; i < 6; ++i) pA[i] = 0.0f;
-            }
-            // gathers (wave-uniform per step): child chains that ended on other lanes
-            if (gw & 1) {          /*@prob:0.09*/
-                const int g0 = f2i(H.in[sr][0][1]), g1 = f2i(H.in[sr][1][1]), g2 = f2i(H.in[sr][2][1]), g3 = f2i(H.in[sr][3][1]);
-                const int mine = f2i(H.in[sr][j][1]);
-                DQ_UNROLL for (int src = 0; src < 4; ++src) {
-                    const int code = src | 8;
-                    bool used = false, want = false;
-                    DQ_UNROLL for (int k = 0; k < 3; ++k) {
-                        used = used || (((g0 >> (4 * k)) & 15) == code) || (((g1 >> (4 * k)) & 15) == code) ||
-                               (((g2 >> (4 * k)) & 15) == code) || (((g3 >> (4 * k)) & 15) == code);
-                        want = want || (((mine >> (4 * k)) & 15) == code);
-                    }
-                    if (used) {
-                        DQ_UNROLL for (int i = 0; i < 21; ++i) {
-                            const float t = src == 0 ? quad_bcast<0>(IA[i]) : (src == 1 ? quad_bcast<1>(IA[i]) : (src == 2 ? quad_bcast<2>(IA[i]) : quad_bcast<3>(IA[i])));
-                            if (want) IA[i] += t;
-                        }
-                        DQ_UNROLL for (int i = 0; i < 6; ++i) {
-                            const float t = src == 0 ? quad_bcast<0>(pA[i]) : (src == 1 ? quad_bcast<1>(pA[i]) : (src == 2 ? quad_bcast<2>(pA[i]) : quad_bcast<3>(pA[i])));
-                            if (want) pA[i] += t;
-                        }
-                    }
-                }
-            }
-            if (b >= 0) {
-                add_rigid_inertia(IA, Mb.Ao, Mb.ho, Mb.mass);
-                DQ_UNROLL for (int i = 0; i < 6; ++i) pA[i] += Mb.pv[i];
-                const float *S = Mb.S;
-                float U[6];
-                DQ_UNROLL for (int r = 0; r < 6; ++r) {
-                    float acc = 0.0f;
-                    DQ_UNROLL for (int c = 0; c < 6; ++c) acc += IA[sym6(r, c)] * S[c];
-                    U[r] = acc;
-                }
-                const float D = dot6(S, U) + Mb.dd;
-                const float Dinv = dw::rcp_nr(D);
-                const float u = Mb.tt - dot6(S, pA);
-                DQ_UNROLL for (int r = 0; r < 6; ++r) {
-                    const float urd = U[r] * Dinv;
-                    DQ_UNROLL for (int c = r; c < 6; ++c) IA[sym6(r, c)] -= urd * U[c];
-                }
-                const float ud = u * Dinv;
-                float pa[6];
-                DQ_UNROLL for (int r = 0; r < 6; ++r) {
-                    float acc = pA[r] + U[r] * ud;
-                    DQ_UNROLL for (int c = 0; c < 6; ++c) acc += IA[sym6(r, c)] * Mb.cb[c];
-                    pa[r] = acc;
-                }
-                DQ_UNROLL for (int r = 0; r < 6; ++r) pA[r] = pa[r];
-                if (X.prim) {
-                    OQ_SLOT(T - 1 - sr, 0, X.pos) = mk4(S[0], S[1], S[2], S[3]);
-                    OQ_SLOT(T - 1 - sr, 1, X.pos) = mk4(S[4], S[5], Dinv, u);
-                    OQ_SLOT(T - 1 - sr, 2, X.pos) = mk4(U[0], U[1], U[2], U[3]);
-                    OQ_SLOT(T - 1 - sr, 3, X.pos) = mk4(U[4], U[5], Mb.qd, 0.0f);
-                }
-            }
-        }
-#endif
         OQ_TOCK(tq_rec);
     }
     wave_sync();
@@ -867,7 +725,6 @@ DQ_HD void oct_substep(OSlots &L, const QHot &H, const QuadModel &QM, const DevM
     {
         float I0[21], p0[6];
         const int g = H.misc[1];
-#if OQ_ROWSPLIT
         {   // every half gathers its rows of the chains below the root; the two halves then put the whole matrix together
             float Dg[6] = {0, 0, 0, 0, 0, 0}, Og[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, pg[3] = {0, 0, 0};
             DQ_UNROLL for (int src = 0; src < 4; ++src) {
@@ -890,20 +747,6 @@ DQ_HD void oct_substep(OSlots &L, const QHot &H, const QuadModel &QM, const DevM
                 p0[r] = rs_all<LPE, 0>(pg[r]); p0[3 + r] = rs_all<LPE, 1>(pg[r]);
             }
         }
-#else
-        DQ_UNROLL for (int i = 0; i < 21; ++i) I0[i] = 0.0f;
-        DQ_UNROLL for (int i = 0; i < 6; ++i) p0[i] = 0.0f;
-        DQ_UNROLL for (int src = 0; src < 4; ++src) {
-            const int code = src | 8;
-            const bool used = ((g & 15) == code) || (((g >> 4) & 15) == code) || (((g >> 8) & 15) == code) || (((g >> 12) & 15) == code);
-            if (used) {
-                DQ_UNROLL for (int i = 0; i < 21; ++i)
-                    I0[i] += src == 0 ? quad_bcast<0>(IA[i]) : (src == 1 ? quad_bcast<1>(IA[i]) : (src == 2 ? quad_bcast<2>(IA[i]) : quad_bcast<3>(IA[i])));
-                DQ_UNROLL for (int i = 0; i < 6; ++i)
-                    p0[i] += src == 0 ? quad_bcast<0>(pA[i]) : (src == 1 ? quad_bcast<1>(pA[i]) : (src == 2 ? quad_bcast<2>(pA[i]) : quad_bcast<3>(pA[i])));
-            }
-        }
-#endif
         // (the base's rotation matrix again from its quaternion: kept from the top of the substep it would cost 9 registers
         //  through the inward pass)
         float R0[9];
@@ -912,11 +755,6 @@ DQ_HD void oct_substep(OSlots &L, const QHot &H, const QuadModel &QM, const DevM
             DQ_OPAQUE(qo4[0]);
             quat_to_mat(qo4, R0);
         }
-#if !OQ_ROWSPLIT
-        // (the recursion of the inward pass is valid in half 0 only: half 1 takes the gathered inertia over)
-        DQ_UNROLL for (int i = 0; i < 21; ++i) I0[i] = LPE == 8 ? oct_lo(I0[i]) : quarter0_all(I0[i]);
-        DQ_UNROLL for (int i = 0; i < 6; ++i) p0[i] = LPE == 8 ? oct_lo(p0[i]) : quarter0_all(p0[i]);
-#endif
         const float v0[6] = {ww[0], ww[1], ww[2], vo[0], vo[1], vo[2]}, x0[3] = {0, 0, 0};
         float Ao[6], ho[3], mass;
         const int base_gym = f2i(H.base[10]), base_ngeom = f2i(H.base[11]);
@@ -1074,9 +912,6 @@ DQ_HD void oct_substep(OSlots &L, const QHot &H, const QuadModel &QM, const DevM
         }
         float hh4[4];
         if (TERRAIN) {
-#if defined(OCT_SAMPLE_ALL)          // (A/B builds only: every lane of the foot samples all four corners, as before round 5)
-            DQ_UNROLL for (int k = 0; k < 4; ++k) dw::terrain_sample(P, X.root[0] + rk[k][0], X.root[1] + rk[k][1], &hh4[k], frame[k]);
-#else
             // The four lanes that work on a foot (2 parts x 2 halves) each sample the height field under ONE corner -- corner part + 2 h --
             // and hand height and frame round: 4 fetches of 2 bytes and one interpolation per lane instead of 16 and four, for two DPP moves
             // per word (the values are the ones every lane computed for itself before: same arithmetic on the same corner)
@@ -1089,7 +924,6 @@ DQ_HD void oct_substep(OSlots &L, const QHot &H, const QuadModel &QM, const DevM
                 hh4[k] = from(ho);
                 DQ_UNROLL for (int i = 0; i < 9; ++i) frame[k][i] = from(fo[i]);
             }
-#endif
         }
         DQ_UNROLL for (int k = 0; k < 4; ++k) {
             float phi = X.root[2] + rk[k][2];
@@ -1104,11 +938,7 @@ DQ_HD void oct_substep(OSlots &L, const QHot &H, const QuadModel &QM, const DevM
     float Pk[4][3];
     DQ_UNROLL for (int k = 0; k < 4; ++k) DQ_UNROLL for (int i = 0; i < 3; ++i) Pk[k][i] = act[k] ? warm[3 * k + i] : 0.0f;
 
-#if defined(OCT_ABL_CONTACT)
-    if (false) {
-#else
     if (any_active) {
-#endif
         // ---- free twist of foot f: base + sum over the leg of S qdf (leg lane), shared with the partner ----
         float twf[6];
         {

@@ -257,7 +257,7 @@ DQ_HD void oct_step(OSlots &L, QHot &HW, const QuadModel &QM, const DevModel &M,
 
     for (int sub = 0; sub < 2; ++sub) {          /*@trip:2*/
         X.stamp_base = 1 + 16 * sub;
-#if !defined(OCT_NO_WG_ALIGN) && defined(__HIPCC__)
+#if defined(__HIPCC__)
         // the two waves of the workgroup meet before every substep: they share nothing but the instruction stream, and in step
         // one instruction fetch serves both (measured: -2 % step time at 16384 envs, nothing at 4096).
         // HARDWARE RULE RELIED UPON: the second wave of the LAST workgroup may have no envs (N mod 16 in 1..8) and returns at the top

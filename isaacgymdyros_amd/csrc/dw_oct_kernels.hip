@@ -28,17 +28,7 @@ void dw_k_step_oct(const dwq::QuadModel *__restrict__ QM, const dw::DevModel *__
     __shared__ dwo::OLds L;
     if (step_dev) step = *step_dev;          // (dw_step_dev: the counter lives in device memory so that a captured launch can be replayed)
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));          // (wave-uniform: keep it in a scalar register)
-#if defined(OCT_STAGGER_SHIFT)      // (timing experiment: hold back every other group of workgroups so that the two waves of a SIMD are in different phases)
-    if ((blockIdx.x >> OCT_STAGGER_SHIFT) & 1) for (int i = 0; i < OCT_STAGGER_SLEEP; ++i) __builtin_amdgcn_s_sleep(127);
-#endif
-#if defined(OCT_FORCE_SCRATCH)      // (timing experiment: what a launch pays for HAVING private memory, with none of it on a hot path)
-    volatile int pad[4];
-    pad[threadIdx.x & 3] = (int)step;
-#endif
     dwo::oct_step<TERRAIN, GPUF, WPE == 1>(L.w[w], L.hot, *QM, *M, P->C, make_obuf(HB, &P->B), actions, mocap, noise, step, (int)blockIdx.x * dwo::WPG + w);
-#if defined(OCT_FORCE_SCRATCH)
-    if (pad[(threadIdx.x + 1) & 3] == 0x7fffffff) __builtin_trap();
-#endif
 }
 // One physics substep at the Gym boundary, same layout.
 template <bool TERRAIN, int WPE>
@@ -149,11 +139,7 @@ void launch_simulate(bool terrain, int wave_build, int num_envs, hipStream_t str
     const dim3 grid(groups(num_envs)), block(64 * WPG);
     const bool sp = spread(num_envs, wave_build);
     if (terrain && sp) hipLaunchKernelGGL((dw_k_simulate_oct<true, 1>), grid, block, 0, stream, QM, M, P, make_hot(B), tau, push);
-#if defined(OCT_SKIP_TSIM2)          // (A/B builds only)
-    else if (terrain) hipLaunchKernelGGL((dw_k_simulate_oct<true, 1>), grid, block, 0, stream, QM, M, P, make_hot(B), tau, push);
-#else
     else if (terrain) hipLaunchKernelGGL((dw_k_simulate_oct<true, 2>), grid, block, 0, stream, QM, M, P, make_hot(B), tau, push);
-#endif
     else if (sp) hipLaunchKernelGGL((dw_k_simulate_oct<false, 1>), grid, block, 0, stream, QM, M, P, make_hot(B), tau, push);
     else hipLaunchKernelGGL((dw_k_simulate_oct<false, 2>), grid, block, 0, stream, QM, M, P, make_hot(B), tau, push);
 }

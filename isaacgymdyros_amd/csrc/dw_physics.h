@@ -101,9 +101,6 @@ DW_HD void motion_cross(const float *v, const float *m, float *c) {
     cross3(v + 3, m, t);
     c[3] += t[0]; c[4] += t[1]; c[5] += t[2];
 }
-DW_HD float dot6(const float *a, const float *b) {
-    return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3] + a[4] * b[4] + a[5] * b[5];
-}
 
 // Height field under a world point (row f-4): bilinear height of the four samples around it, unit normal from that
 // patch's gradient, contact frame (t1, t2, n) with t1 = world x projected into the tangent plane (oracle/dw_physics.c
@@ -166,9 +163,6 @@ DW_HD int16_t terrain_bound_cell(const int16_t *hs, int rows, int cols, int cell
 }
 // the height no point of the field within reach of a robot based at world (x, y) exceeds (same index arithmetic as terrain_sample)
 DW_HD float terrain_bound(const PhysParams &P, float x, float y) {
-#if defined(DW_NO_TERRAIN_BOUND)          // (A/B builds only: every body with primitives samples the field, as before round 4)
-    return 3.0e38f;
-#endif
     if (!P.hmax) return 3.0e38f;
     float u = (x + P.t_border) * P.t_inv_h, v = (y + P.t_border) * P.t_inv_h;
     const float umax = (float)(P.t_rows - 1) - 1e-3f, vmax = (float)(P.t_cols - 1) - 1e-3f;

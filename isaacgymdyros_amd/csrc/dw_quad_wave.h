@@ -12,7 +12,7 @@
 //   quad_xor1(x)/quad_xor2 value of x in lane (l ^ 1) / (l ^ 2)                 (quad_perm:[1,0,3,2] / [2,3,0,1])
 //   oct_xor4(x)            value of x in lane (l ^ 4)  (octet kernels)           (row_shl:4 / row_shr:4, complementary bank masks)
 //   oct_lo(x) / oct_hi(x)  value of x in lane (l & ~4) / (l | 4) (octet kernels) (row_shr:4 into the high quads / row_shl:4 into the low quads)
-//   oct_take_lo / _hi(own, src): one half of a limb takes ANOTHER register of the other half's lane, the other half keeps `own`
+//   rs_take / rs_all       the row-split recursion's hand-over between the halves (quarters) of a limb (below)
 //   oct_fetch(x, src)      x of lane (l & ~7) | src of the caller's octet, src per lane (ds_bpermute)
 //   quad_xor1_hi / quad_pair_lo / quad_pair_hi: one-move forms of `cond ? exchanged : own` (below)
 //   wave_any(p)            true in every lane iff p holds in some lane           (v_cmp + s_cmp on the ballot)
@@ -67,15 +67,6 @@ DQ_HD float oct_hi(float x) {
     const int xi = __builtin_bit_cast(int, x);
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(xi, xi, 0x104, 0xF, 0x5, false));
 }
-// selections across the halves of a limb with DIFFERENT registers on the two sides (the row-split recursion of dw_oct.h):
-//   oct_take_lo(own, src)   half-1 lanes take src of lane l - 4, half-0 lanes keep `own`   (row_shr:4 into the high quads)
-//   oct_take_hi(own, src)   half-0 lanes take src of lane l + 4, half-1 lanes keep `own`   (row_shl:4 into the low quads)
-DQ_HD float oct_take_lo(float own, float src) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, own), __builtin_bit_cast(int, src), 0x114, 0xF, 0xA, false));
-}
-DQ_HD float oct_take_hi(float own, float src) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, own), __builtin_bit_cast(int, src), 0x104, 0xF, 0x5, false));
-}
 // selections that a lane-dependent `cond ? exchanged : own` would spend a move AND a select on, as ONE move:
 //   quad_xor1_hi(x)   half-1 lanes (l & 4) take x of lane l ^ 1, half-0 lanes keep their own (bank mask: the high quads of a row)
 //   quad_pair_lo(x)   x of the lane (l & ~2) of my pair {l, l ^ 2};  quad_pair_hi(x): of the lane (l | 2)
@@ -93,16 +84,10 @@ DQ_HD float quad_pair_hi(float x) { return dpp_quad<2 | (3 << 2) | (2 << 4) | (3
 // The 16-lanes-per-env ("hex") instantiation of the octet kernels (dw_oct.h, OCT_LPE = 16): an env is one DPP row, four QUARTERS
 // q = (l >> 2) & 3 of four limb lanes each.
 //   hex_xor8(x)          x of lane l ^ 8 (the other octet of the row)                      (row_ror:8)
-//   quarter_take<K>(x)   quarter-0 lanes take x of lane l + 4 K (quarter K, same limb); other lanes keep theirs  (row_shl:4K, bank 0)
 //   quarter0_all(x)      every lane takes x of lane l & ~12 (quarter 0, same limb)          (three bank-masked row_shr moves)
 DQ_HD float hex_xor8(float x) {
     const int xi = __builtin_bit_cast(int, x);
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(xi, xi, 0x128, 0xF, 0xF, false));
-}
-template <int K> DQ_HD float quarter_take(float x) {
-    static_assert(K >= 1 && K <= 3, "quarter_take: K = 1..3");
-    const int xi = __builtin_bit_cast(int, x);
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(xi, xi, 0x100 + 4 * K, 0xF, 0x1, false));
 }
 DQ_HD float quarter0_all(float x) {
     const int xi = __builtin_bit_cast(int, x);

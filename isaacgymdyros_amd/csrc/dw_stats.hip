@@ -17,14 +17,8 @@ char s_err[256] = "";
 int fail(const char *msg) { snprintf(s_err, sizeof(s_err), "%s", msg); return -1; }
 int fail_hip(const char *who, hipError_t e) { snprintf(s_err, sizeof(s_err), "%s: %s", who, hipGetErrorString(e)); return -1; }
 
-#ifndef DWS_EPB
-#define DWS_EPB 32
-#endif
-#ifndef DWS_TPB
-#define DWS_TPB 128
-#endif
 // envs and lanes per workgroup: 32 / 128 measured fastest at 16384 envs against 16 / 128, 16 / 64, 8 / 128, 8 / 64, 4 / 64
-constexpr int EPB = DWS_EPB, TPB = DWS_TPB;
+constexpr int EPB = 32, TPB = 128;
 constexpr int CFW = EPB * dws::NB * 3;              // contact words of a workgroup
 constexpr int TQW = 12;                             // action_torque
 static_assert(EPB <= TPB && TPB % 64 == 0, "one lane per env");

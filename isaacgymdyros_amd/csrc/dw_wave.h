@@ -33,13 +33,9 @@ struct Wave {
         // End of region.  The workgroup IS the wave, and a wave's LDS instructions execute in program order, so
         // no s_barrier (and no vmcnt drain) is needed: a wavefront-scope fence keeps the compiler from moving
         // LDS/global accesses across the region boundary and emits no instruction.
-#if defined(DW_REGION_SYNCTHREADS)
-        __syncthreads();
-#else
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#endif
     }
     template <class F> DW_HD void simt(F &&f) const { par(f); }
 };

@@ -150,8 +150,6 @@ DQ_HD float quad_xor2(float x) { return emu_xchg(x, g_emu->cur ^ 2); }
 DQ_HD float oct_xor4(float x) { return emu_xchg(x, g_emu->cur ^ 4); }
 DQ_HD float oct_lo(float x) { return emu_xchg(x, g_emu->cur & ~4); }
 DQ_HD float oct_hi(float x) { return emu_xchg(x, g_emu->cur | 4); }
-DQ_HD float oct_take_lo(float own, float src) { const float t = emu_xchg(src, g_emu->cur & ~4); return (g_emu->cur & 4) ? t : own; }
-DQ_HD float oct_take_hi(float own, float src) { const float t = emu_xchg(src, g_emu->cur | 4); return (g_emu->cur & 4) ? own : t; }
 template <int LPE_, int K> DQ_HD float rs_take(float a, float b) {
     const int l = g_emu->cur, q = (l >> 2) & (LPE_ / 4 - 1), src = l - 4 * q + 4 * K;
     const float ta = emu_xchg(a, src), tb = emu_xchg(b, src);
@@ -172,7 +170,6 @@ DQ_HD float half_bits_to_float(int h) {          // (positive normal numbers and
 DQ_HD float quad_pair_lo(float x) { return emu_xchg(x, g_emu->cur & ~2); }
 DQ_HD float quad_pair_hi(float x) { return emu_xchg(x, g_emu->cur | 2); }
 DQ_HD float hex_xor8(float x) { return emu_xchg(x, g_emu->cur ^ 8); }
-template <int K> DQ_HD float quarter_take(float x) { return emu_xchg(x, (g_emu->cur & 12) == 0 ? g_emu->cur + 4 * K : g_emu->cur); }
 DQ_HD float quarter0_all(float x) { return emu_xchg(x, g_emu->cur & ~12); }
 DQ_HD bool wave_any(bool p) {
     WaveEmu *e = g_emu;

@@ -1,5 +1,5 @@
-"""Distribution of the wave lifetimes of one step-kernel launch (library built with -DDQ_WAVE_TIME: tools/abl_build.sh DQ_WAVE_TIME for
-the octet kernels, tools/ab_lib.sh wt -DDQ_WAVE_TIME + DW_PIPE=2 for the quad kernels; every wave leaves its cycle count in stacked_rewards[first env of the wave, 14])."""
+"""Distribution of the wave lifetimes of one step-kernel launch (library built with -DDQ_WAVE_TIME:
+tools/tu_lib.sh libdw_wt dw_oct_kernels.hip -DDQ_WAVE_TIME; every wave leaves its cycle count in stacked_rewards[first env of the wave, 14])."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
