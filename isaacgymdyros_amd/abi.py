@@ -1,4 +1,4 @@
-"""ctypes mirror of include/dyros_walk.h: the structs by hand; the constants and the function prototypes are read from the header (cbind.py).
+"""ctypes mirror of include/dyros_walk.h: the constants, the structs and the function prototypes are all read from the header (cbind.py).
 
 The reference binds its native engine through pybind11 (`gym_3x.so`) and aliases sim-owned buffers
 with `gymtorch.wrap_tensor` (reference: python/isaacgym/gymtorch.py:61-106).  Here buffers are
@@ -10,114 +10,18 @@ import ctypes as C
 import os
 
 from . import cbind
-from .model import DwModel, DwGeom  # noqa: F401  (re-exported)
 
 HEADER = os.path.join(cbind.INCLUDE, "dyros_walk.h")
 K = cbind.constants("dyros_walk.h", "dw_")          # every integer #define of the header, e.g. K["DW_ES_WORDS"]
 globals().update(K)
-
-
-class DwTaskConst(C.Structure):
-    _fields_ = [(n, C.POINTER(C.c_float)) for n in
-                ("kp", "kv", "action_high", "initial_dof_pos", "mocap", "obs_mean", "obs_var",
-                 "dof_armature_nominal", "dof_damping_nominal")]
-
-
-class DwConfig(C.Structure):
-    _fields_ = [
-        ("dt", C.c_double),
-        ("num_envs", C.c_int32),
-        ("control_freq_inv", C.c_int32),
-        ("gravity", C.c_float * 3),
-        ("solver_iterations", C.c_int32),
-        ("contact_offset", C.c_float),
-        ("max_depenetration_velocity", C.c_float),
-        ("friction", C.c_float),
-        ("erp", C.c_float),
-        ("contact_cfm", C.c_float),
-        ("penalty_stiffness", C.c_float),
-        ("penalty_damping", C.c_float),
-        ("max_angular_velocity", C.c_float),
-        ("max_episode_length", C.c_float),
-        ("initial_height", C.c_float),
-        ("death_cost", C.c_float),
-        ("perturb", C.c_int32),
-        ("force_perturb_start", C.c_int32),
-        ("randomize_dof_on_reset", C.c_int32),
-        ("dr_damping_add", C.c_float * 2),
-        ("dr_armature_scale", C.c_float * 2),
-        ("randomize_friction_on_reset", C.c_int32),
-        ("dr_friction_scale", C.c_float * 2),
-        ("timeout_fix", C.c_int32),
-        ("root_vel_at_com", C.c_int32),
-        ("torch_gpu_div", C.c_int32),
-        ("self_collision", C.c_int32),
-        ("debug_freeze_physics", C.c_int32),
-        ("seed", C.c_uint64),
-        ("terrain", C.c_int32),
-        ("terrain_rows", C.c_int32),
-        ("terrain_cols", C.c_int32),
-        ("terrain_hscale", C.c_float),
-        ("terrain_vscale", C.c_float),
-        ("terrain_border", C.c_float),
-        ("terrain_curriculum", C.c_int32),
-        ("terrain_num_levels", C.c_int32),
-        ("terrain_num_types", C.c_int32),
-        ("terrain_env_length", C.c_float),
-        ("max_episode_length_s", C.c_float),
-        ("custom_origins", C.c_int32),
-        ("pipeline", C.c_int32),
-        ("debug_wave_build", C.c_int32),
-    ]
-
-
-_F = C.c_void_p   # device (or, for the oracle, host) pointers travel as plain addresses
-
-
-class DwBuffers(C.Structure):
-    _fields_ = [(n, _F) for n in (
-        "root_states", "dof_state", "contact_forces",
-        "mass_scale", "dof_damping", "dof_armature", "friction_scale", "total_mass", "env_origins",
-        "obs_buf", "rew_buf", "reset_buf", "progress_buf", "timeout_buf", "randomize_buf",
-        "stacked_rewards", "env_state", "obs_history", "action_history", "gate_acc",
-        "height_samples", "terrain_origins", "terrain_levels", "terrain_types")]
-
-
-BUFFER_NAMES = [n for n, _ in DwBuffers._fields_]
-
-
-AMP_BUFFER_NAMES = ["actions", "actions_pre", "action_history", "obs_history", "commands", "start_target_vel", "final_target_vel",
-                    "vel_change_duration", "cur_vel_change_duration", "epi_len", "power_scale", "action_log", "delay_idx", "simul_len",
-                    "qpos_noise", "qvel_noise", "qpos_pre", "qpos_bias", "quat_bias", "dof_vel_pre", "tau", "progress_buf", "randomize_buf",
-                    "reset_buf", "terminate_buf", "timeout_buf", "rigid_body_pos", "rigid_body_rot", "foot_pos", "obs1", "obs_buf", "obs_out",
-                    "rew_buf", "reward_values", "total_mass", "amp_obs_buf", "amp_obs1", "motor_efforts", "p_gains", "d_gains", "init_angle",
-                    "pd_action_offset", "pd_action_scale", "epi_len_log", "perturbation_count", "perturb_timing", "pert_on", "initial_root_states",
-                    "hist_head", "draw_ctr", "nominal_damping", "nominal_armature"]
-
-
-class DwAmpBuffers(C.Structure):            # include/dyros_walk.h, the fused TocabiAMPLower step
-    _fields_ = [(n, C.c_void_p) for n in AMP_BUFFER_NAMES]
-
-
-class DwAmpConfig(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("num_envs", "num_his", "num_skip", "log_slots", "amp_steps", "pd_control", "noise", "vel_change",
-                                         "local_root_obs", "enable_early_termination")] + \
-               [(n, C.c_float) for n in ("clip_actions", "clip_obs", "max_episode_length", "termination_height", "inv_dt", "dt")] + \
-               [("gpu_div", C.c_int32), ("cmd_lo", C.c_float * 3), ("cmd_scale", C.c_float * 3)] + \
-               [(n, C.c_int32) for n in ("hist_ring", "device_draws", "randomize", "dr_damping", "dr_armature", "dr_frequency")] + \
-               [("dr_damping_range", C.c_float * 2), ("dr_armature_range", C.c_float * 2), ("delay_idx_range", C.c_int32 * 2), ("seed", C.c_uint64)]
-
-
-AMP_RESET_DRAW_NAMES = ["power_scale_u", "rootvel_noise", "cmd_x_u", "cmd_y_u", "cmd_yaw_u", "qpos_bias_u", "quat_bias_u", "damping_u", "armature_u",
-                        "perturb_timing", "delay_idx"]
-
-
-class DwAmpResetDraws(C.Structure):         # include/dyros_walk.h: the caller's draws of dw_amp_reset_done, rows indexed by env
-    _fields_ = [(n, C.c_void_p) for n in AMP_RESET_DRAW_NAMES]
-
-
-STRUCTS = (DwConfig, DwModel, DwTaskConst, DwBuffers, DwAmpBuffers, DwAmpConfig, DwAmpResetDraws)
-EXPORTS = list(cbind.signatures("dyros_walk.h", "dw_", STRUCTS))
+S = cbind.structs("dyros_walk.h", "dw_")            # every struct of the header as a ctypes.Structure, e.g. S["DwConfig"]
+globals().update(S)
+STRUCTS = tuple(S.values())
+# the three pointer tables: device (or, for the oracle, host) pointers travel as plain addresses
+BUFFER_NAMES = [n for n, _ in S["DwBuffers"]._fields_]
+AMP_BUFFER_NAMES = [n for n, _ in S["DwAmpBuffers"]._fields_]             # the fused TocabiAMPLower step
+AMP_RESET_DRAW_NAMES = [n for n, _ in S["DwAmpResetDraws"]._fields_]      # the caller's draws of dw_amp_reset_done, rows indexed by env
+EXPORTS = list(cbind.signatures("dyros_walk.h", "dw_"))
 # The fused TocabiAMPLower step (csrc/dw_amp_step.h) is carried by the HIP library and by the octet build of the host emulation
 # (tests/emul/), its one-launch form and dw_amp_reset_ids by the HIP library alone; the C oracle has neither, nor dw_terrain_log.
 _FUSED_AMP = ("amp_step_begin", "amp_step_mid", "amp_step_end", "amp_step", "amp_reset_rows", "amp_reset_done", "amp_reset_ids")
@@ -130,7 +34,7 @@ MAY_LACK = {"dw_": (),
 def declare(lib: C.CDLL, prefix: str = "dw_"):
     """Every entry point bound with the types its prototype in the header has (cbind); raises AttributeError if the shared object lacks one of
     them that a library of this prefix has to export, DyrosWalkLibraryError if its ABI version is not the header's."""
-    return cbind.declare(lib, "dyros_walk.h", "dw_", STRUCTS, symbols=prefix, may_lack=MAY_LACK[prefix])
+    return cbind.declare(lib, "dyros_walk.h", "dw_", symbols=prefix, may_lack=MAY_LACK[prefix])
 
 
 # name -> (per-env shape, numpy dtype string); gate_acc is the one buffer without an env dimension

@@ -217,15 +217,12 @@ def _req(name, t, dtype, device, shape):
     return t
 
 
-class DwdLoss(C.Structure):          # include/dyros_amp_disc.h
-    _fields_ = [("disc_coef", C.c_float), ("logit_reg", C.c_float), ("grad_penalty", C.c_float), ("weight_decay", C.c_float)]
-
-
-EXPORTS = list(cbind.signatures("dyros_amp_disc.h", "dwd_", (DwdLoss,)))
+DwdLoss = cbind.structs("dyros_amp_disc.h", "dwd_")["DwdLoss"]
+EXPORTS = list(cbind.signatures("dyros_amp_disc.h", "dwd_"))
 
 
 def declare(lib: C.CDLL) -> dict:
-    return cbind.declare(lib, "dyros_amp_disc.h", "dwd_", (DwdLoss,))
+    return cbind.declare(lib, "dyros_amp_disc.h", "dwd_")
 
 
 class AmpDiscriminator:

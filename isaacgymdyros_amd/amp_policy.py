@@ -91,15 +91,12 @@ def loss_terms(old_nlp, nlp, adv, mu, v, ret_n, e_clip):
     return a_loss, c_loss, b_loss, clip_frac
 
 
-class DwaLoss(C.Structure):          # include/dyros_amp_policy.h
-    _fields_ = [("e_clip", C.c_float), ("critic_coef", C.c_float), ("bounds_coef", C.c_float)]
-
-
-EXPORTS = list(cbind.signatures("dyros_amp_policy.h", "dwa_", (DwaLoss,)))
+DwaLoss = cbind.structs("dyros_amp_policy.h", "dwa_")["DwaLoss"]
+EXPORTS = list(cbind.signatures("dyros_amp_policy.h", "dwa_"))
 
 
 def declare(lib: C.CDLL) -> dict:
-    return cbind.declare(lib, "dyros_amp_policy.h", "dwa_", (DwaLoss,))
+    return cbind.declare(lib, "dyros_amp_policy.h", "dwa_")
 
 
 def _api():

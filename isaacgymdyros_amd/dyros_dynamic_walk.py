@@ -173,7 +173,7 @@ class DyrosDynamicWalk(VecTask):
         for k, _ in abi.DwTaskConst._fields_:
             arr = np.ascontiguousarray(self._tc[k], dtype=np.float32).ravel()
             self._tc_keep[k] = arr
-            setattr(tc, k, arr.ctypes.data_as(C.POINTER(C.c_float)))
+            setattr(tc, k, arr.ctypes.data)
         self._cmodel = self.model.to_c()
         h = C.c_void_p()
         _lib.check(self._api, self._api["create"](C.byref(self._ccfg), C.byref(self._cmodel), C.byref(tc), C.byref(h)))

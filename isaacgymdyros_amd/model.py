@@ -22,7 +22,6 @@ reference checkout is present (``tools/compile_assets.py``).
 """
 from __future__ import annotations
 
-import ctypes
 import json
 import math
 import os
@@ -31,17 +30,16 @@ from typing import Dict, List
 
 import numpy as np
 
+from . import cbind
+
 ASSET_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets")
 MODEL_JSON = os.path.join(ASSET_DIR, "tocabi_model.json")
 
-NUM_BODIES = 38   # Gym rigid bodies (reference: SURVEY appendix A)
-NUM_MOVING = 34   # floating base + 33 hinge links
-NUM_DOF = 33
-NUM_INERT = 36
-MAX_GEOMS = 64
-NUM_FOOT_PTS = 8
-MAX_SC_PROXIES = 16
-MAX_SC_PAIRS = 64
+# the model's fixed sizes, as include/dyros_walk.h has them: 38 Gym rigid bodies (reference: SURVEY appendix A), 34 moving ones (floating base +
+# 33 hinge links), 33 DoF, 36 inertial records, and the capacities of the geometry, sole-point and self-collision tables
+(NUM_BODIES, NUM_MOVING, NUM_DOF, NUM_INERT, MAX_GEOMS, NUM_FOOT_PTS, MAX_SC_PROXIES, MAX_SC_PAIRS) = (
+    cbind.constants("dyros_walk.h", "dw_")["DW_" + n] for n in ("NUM_BODIES", "NUM_MOVING", "NUM_DOF", "NUM_INERT", "MAX_GEOMS", "NUM_FOOT_PTS",
+                                                               "MAX_SC_PROXIES", "MAX_SC_PAIRS"))
 # links that get a self-collision capsule: (left, right) chains thigh / shank / ankle / foot assembly ...
 SC_LEG_BODIES = ("Thigh_Link", "Knee_Link", "AnkleCenter_Link", "Foot_Redundant_Link")
 # ... and, second tranche ("leg<->leg, arm<->torso/leg"): upper arm, forearm, hand of each arm and the torso
@@ -364,49 +362,9 @@ def compile_mjcf(xml_path: str) -> Dict:
 
 
 # ---------------------------------------------------------------------------------------
-# C mirror of include/dyros_walk.h :: DwModel
+# include/dyros_walk.h :: DwModel and the two structs it embeds, read from the header (cbind.py)
 # ---------------------------------------------------------------------------------------
-class DwGeom(ctypes.Structure):
-    _fields_ = [("type", ctypes.c_int), ("moving", ctypes.c_int), ("gym", ctypes.c_int),
-                ("sole", ctypes.c_int),
-                ("pos", ctypes.c_float * 3), ("rot", ctypes.c_float * 9),
-                ("size", ctypes.c_float * 3), ("_pad", ctypes.c_float)]
-
-
-class DwCapsule(ctypes.Structure):
-    _fields_ = [("moving", ctypes.c_int), ("gym", ctypes.c_int), ("p0", ctypes.c_float * 3), ("p1", ctypes.c_float * 3),
-                ("radius", ctypes.c_float)]
-
-
-class DwModel(ctypes.Structure):
-    _fields_ = [
-        ("mv_parent", ctypes.c_int * NUM_MOVING),
-        ("mv_gym", ctypes.c_int * NUM_MOVING),
-        ("mv_depth", ctypes.c_int * NUM_MOVING),
-        ("mv_pos", (ctypes.c_float * 3) * NUM_MOVING),
-        ("mv_rot0", (ctypes.c_float * 9) * NUM_MOVING),
-        ("mv_axis", (ctypes.c_float * 3) * NUM_MOVING),
-        ("dof_lower", ctypes.c_float * NUM_DOF),
-        ("dof_upper", ctypes.c_float * NUM_DOF),
-        ("dof_vmax", ctypes.c_float * NUM_DOF),
-        ("inert_mv", ctypes.c_int * NUM_INERT),
-        ("inert_gym", ctypes.c_int * NUM_INERT),
-        ("inert_mass", ctypes.c_float * NUM_INERT),
-        ("inert_com", (ctypes.c_float * 3) * NUM_INERT),
-        ("inert_I", (ctypes.c_float * 6) * NUM_INERT),   # xx yy zz xy xz yz about the COM
-        ("num_geoms", ctypes.c_int),
-        ("geoms", DwGeom * MAX_GEOMS),
-        ("foot_mv", ctypes.c_int * NUM_FOOT_PTS),
-        ("foot_gym", ctypes.c_int * NUM_FOOT_PTS),
-        ("foot_pos", (ctypes.c_float * 3) * NUM_FOOT_PTS),
-        ("left_foot_gym", ctypes.c_int),
-        ("right_foot_gym", ctypes.c_int),
-        ("pelvis_gym", ctypes.c_int),
-        ("num_sc_proxies", ctypes.c_int),
-        ("sc_proxy", DwCapsule * MAX_SC_PROXIES),
-        ("num_sc_pairs", ctypes.c_int),
-        ("sc_pair", (ctypes.c_int * 2) * MAX_SC_PAIRS),
-    ]
+DwGeom, DwCapsule, DwModel = (cbind.structs("dyros_walk.h", "dw_")[n] for n in ("DwGeom", "DwCapsule", "DwModel"))
 
 
 @dataclass

@@ -59,18 +59,14 @@ def _req(name: str, t, dtype, numel: int = None, shape: tuple = None):
     return t
 
 
-class DwpMlp(C.Structure):          # include/dyros_ppo.h
-    _fields_ = [(n, C.c_void_p) for n in ("obs", "state", "act", "old_nlp", "old_mu", "adv", "ret", "logstd", "obs16", "p16", "p16t", "pbuf",
-                                          "x16", "h1", "h2", "out16", "dout16", "dz2", "dz1", "xf", "h1f", "h2f", "doutf", "dz2f", "dz1f")] + [("B", C.c_int32), ("e_clip", C.c_float), ("critic_coef", C.c_float)]
-
-
-EXPORTS = list(cbind.signatures("dyros_ppo.h", "dwp_", (DwpMlp,)))
+DwpMlp = cbind.structs("dyros_ppo.h", "dwp_")["DwpMlp"]
+EXPORTS = list(cbind.signatures("dyros_ppo.h", "dwp_"))
 
 
 def declare(lib: C.CDLL) -> dict:
-    api = cbind.declare(lib, "dyros_ppo.h", "dwp_", (DwpMlp,))
+    api = cbind.declare(lib, "dyros_ppo.h", "dwp_")
     if api["sizeof_mlp"]() != C.sizeof(DwpMlp):
-        raise _lib.DyrosWalkLibraryError("include/dyros_ppo.h: DwpMlp is %d bytes in the library and %d in isaacgymdyros_amd/ppo_update.py: rebuild"
+        raise _lib.DyrosWalkLibraryError("DwpMlp is %d bytes in the library and %d in include/dyros_ppo.h: rebuild"
                                          % (api["sizeof_mlp"](), C.sizeof(DwpMlp)))
     return api
 

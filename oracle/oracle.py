@@ -94,11 +94,10 @@ class OracleSim:
         if task_const is not None:
             tc = abi.DwTaskConst()
             keep = {}
-            for k in ("kp", "kv", "action_high", "initial_dof_pos", "mocap", "obs_mean", "obs_var",
-                      "dof_armature_nominal", "dof_damping_nominal"):
+            for k, _ in abi.DwTaskConst._fields_:
                 arr = np.ascontiguousarray(task_const[k], dtype=np.float32).ravel()
                 keep[k] = arr
-                setattr(tc, k, arr.ctypes.data_as(C.POINTER(C.c_float)))
+                setattr(tc, k, arr.ctypes.data)
             self._task_keep = (tc, keep)
             tptr = C.byref(tc)
         h = C.c_void_p()

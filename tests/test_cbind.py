@@ -1,11 +1,13 @@
 """The ctypes bindings of the five C ABIs are read from their headers (isaacgymdyros_amd/cbind.py).  ctypes passes arguments by position and
 checks nothing: a C signature that gained a parameter while the binding kept the old list hands a kernel the NEXT argument as its pointer
 (the r5m4 memory fault).  The binding and the header now have one source, so these tests hold it against things the
-binding's parser did not produce: a dumb regex over the header, the built library, and signatures written out here.  No GPU."""
+binding's parser did not produce: a dumb regex over the header, the built library, the host compiler's layout of every struct, and
+signatures and structs written out here.  No GPU."""
 import ctypes as C
 import importlib
 import os
 import re
+import subprocess
 
 import pytest
 
@@ -75,6 +77,8 @@ def test_signatures_written_out():
     dwp = cbind.signatures("dyros_ppo.h", "dwp_", (ppo_update.DwpMlp,))
     dwa = cbind.signatures("dyros_amp_policy.h", "dwa_", (amp_policy.DwaLoss,))
     dwd = cbind.signatures("dyros_amp_disc.h", "dwd_", (amp_disc.DwdLoss,))
+    assert (walk, dwp, dwa, dwd) == (cbind.signatures("dyros_walk.h", "dw_"), cbind.signatures("dyros_ppo.h", "dwp_"),      # the default:
+                                     cbind.signatures("dyros_amp_policy.h", "dwa_"), cbind.signatures("dyros_amp_disc.h", "dwd_"))  # the header's own
     assert dwp["rollout_post"] == (C.c_int, [P, P, P, P, I, P, P, P, I, I, F, F, P, P, I, P, P, I, P])
     assert dwp["mlp"] == (C.c_int, [C.POINTER(ppo_update.DwpMlp), P])
     assert walk["step"] == (C.c_int, [P, P, P, I64, P])
@@ -100,6 +104,94 @@ def test_a_declaration_outside_the_header_style_is_refused(proto):
         cbind.signatures("none.h", "dwx_", (), source="int dwx_abi_version(void);\n" + proto)
     assert list(cbind.signatures("none.h", "dwx_", (), source="int dwx_abi_version(void);\nint64_t dwx_g(const float *const *z, int64_t n);")) \
         == ["abi_version", "g"]
+
+
+@pytest.mark.parametrize("body", ["unsigned int n;",                         # a base type that is not one of the fixed-width names
+                                  "DwxLater s;",                            # ... or a struct the header has not defined by then
+                                  "float a[DWX_M];",                        # a dimension that is neither a number nor a define of the header
+                                  "int32_t a : 3;",                         # a bit-field
+                                  "union { int32_t i; float f; } u;",       # a union
+                                  "struct { int32_t i; } s;",               # a nested, anonymous struct definition
+                                  "int (*cb)(int);",                        # a function pointer
+                                  "float **p;",                             # a pointer to a pointer
+                                  "const float *const *z;",
+                                  "float *a[2];"])                          # an array of pointers
+def test_a_struct_outside_the_header_style_is_refused(body):
+    with pytest.raises(TypeError, match="DwxBad"):
+        cbind.structs("none.h", "dwx_", source="#define DWX_N 4\ntypedef struct DwxBad {\n    float x[DWX_N];\n    %s\n} DwxBad;" % body)
+
+
+@pytest.mark.parametrize("source, named", [("typedef struct DwxBad { int32_t a; } DwxOther;", "DwxBad"),     # tag and typedef name differ
+                                           ("typedef struct { int32_t a; } DwxBad;", "unnamed"),
+                                           ("typedef struct DwxBad { int32_t a; } DwxBad, *DwxPtr;", "DwxBad")])
+def test_a_struct_block_that_was_not_read_is_refused(source, named):
+    with pytest.raises(TypeError, match="not read as structs: .*" + named):
+        cbind.structs("none.h", "dwx_", source="typedef struct DwxGood { int32_t a; } DwxGood;\n" + source)
+
+
+def test_structs_written_out():
+    """One well-formed header with every form the style allows, against ctypes classes written out here: several declarators of one base
+    type, a const pointer, every scalar width, a 2-D array with a macro dimension, an embedded array of an earlier struct; the opaque handle
+    typedef is no struct."""
+    S = cbind.structs("none.h", "dwx_", source="""
+        #define DWX_N 4   /* rows */
+        typedef struct DwxIn { int32_t a, b; float v[3]; } DwxIn;
+        typedef struct DwxHandle DwxHandle;
+        typedef struct DwxOut {
+            const float *p, *q;      /* [N] each */
+            uint8_t *flags; int64_t *ids;
+            double  t;
+            int16_t m[DWX_N][2];     /* rows of two */
+            uint16_t h; uint8_t c;
+            DwxIn   inner[DWX_N], last;
+            uint64_t seed; int n; int64_t k;
+        } DwxOut;
+        int dwx_f(const DwxOut *o, DwxIn i);""")
+    assert list(S) == ["DwxIn", "DwxOut"] and [s.__name__ for s in S.values()] == list(S) and all(issubclass(s, C.Structure) for s in S.values())
+    assert S["DwxIn"]._fields_ == [("a", C.c_int32), ("b", C.c_int32), ("v", C.c_float * 3)]
+    assert S["DwxOut"]._fields_ == [("p", C.c_void_p), ("q", C.c_void_p), ("flags", C.c_void_p), ("ids", C.c_void_p), ("t", C.c_double),
+                                    ("m", (C.c_int16 * 2) * 4), ("h", C.c_uint16), ("c", C.c_uint8), ("inner", S["DwxIn"] * 4),
+                                    ("last", S["DwxIn"]), ("seed", C.c_uint64), ("n", C.c_int), ("k", C.c_int64)]
+    assert (C.sizeof(S["DwxIn"]), C.sizeof(S["DwxOut"]), S["DwxOut"].inner.offset, S["DwxOut"].seed.offset) == (20, 184, 60, 160)
+    # a pointer field takes what a c_void_p parameter takes: an address, None, a typed pointer
+    o, a = S["DwxOut"](), (C.c_float * 2)()
+    o.p, o.q, o.flags = C.addressof(a), C.cast(a, C.POINTER(C.c_float)), None
+    assert (o.p, o.q, o.flags) == (C.addressof(a), C.addressof(a), None)
+
+
+@pytest.mark.parametrize("header, prefix, module", ABIS, ids=[a[1].rstrip("_") for a in ABIS])
+def test_struct_layouts_match_the_host_compiler(header, prefix, module, tmp_path):
+    """For every ABI: a C program that includes the header prints sizeof(S), and offsetof(S, f) and sizeof(S.f) of every field the binding
+    has; built by the compiler of the host emulation (tests/emul) and run, its output is the layout of the ctypes classes.  A field the
+    binding lacks shows as another sizeof(S), a reordered or mistyped one as another offset or size.  And, by a regex that is not the
+    binding's: the identifiers in front of `,` `;` `[` in each struct's body are the class's field names, in order; the modules' classes
+    are these."""
+    S = cbind.structs(header, prefix)
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
+    assert re.findall(r"typedef\s+struct\s+(\w+)\s*\{", src) == list(S)
+    mod = importlib.import_module("isaacgymdyros_amd." + module)
+    for name, cls in S.items():
+        body = src[src.index("typedef struct %s {" % name):src.index("} %s;" % name)].split("{", 1)[1]
+        assert re.findall(r"([A-Za-z_]\w*)\s*[,;\[]", body) == [f for f, _ in cls._fields_], name
+        assert getattr(mod, name) is cls
+    lines, want = [], []
+    for name, cls in S.items():
+        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (name, name))
+        want.append("%s %d" % (name, C.sizeof(cls)))
+        for f, _ in cls._fields_:
+            lines.append('printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (name, f, name, f, name, f))
+            want.append("%s.%s %d %d" % (name, f, getattr(cls, f).offset, getattr(cls, f).size))
+    (tmp_path / "layout.cpp").write_text('#include <stddef.h>\n#include <stdio.h>\n#include "%s"\nint main(void) {\n%s\nreturn 0;\n}\n'
+                                         % (header, "\n".join(lines)))
+    exe = str(tmp_path / "layout")
+    subprocess.run([os.environ.get("CXX", "g++"), "-I", os.path.join(ROOT, "include"), "-o", exe, str(tmp_path / "layout.cpp")], check=True)
+    assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines() == want
+
+
+def test_the_abi_name_lists_are_the_pointer_tables():
+    """The three name lists callers fill the pointer tables by are the structs' fields, every one a plain address."""
+    for cls, names in ((abi.DwBuffers, abi.BUFFER_NAMES), (abi.DwAmpBuffers, abi.AMP_BUFFER_NAMES), (abi.DwAmpResetDraws, abi.AMP_RESET_DRAW_NAMES)):
+        assert [(n, C.c_void_p) for n in names] == cls._fields_ and C.sizeof(cls) == 8 * len(names) > 0
 
 
 def test_a_library_of_another_abi_version_or_without_a_symbol_is_refused():
