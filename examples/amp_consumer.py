@@ -77,7 +77,7 @@ class ActorCritic(nn.Module):
         return v * torch.sqrt(r.running_var.float() + r.epsilon) + r.running_mean.float()
 
 
-def make_env(n, device, motion_file, synthetic):
+def make_env(n, device, motion_file, synthetic, motion_device=False):
     from isaacgymdyros_amd.tocabi_amp_lower import TocabiAMPLower, default_amp_cfg
     cfg = default_amp_cfg(n, device)
     if synthetic:
@@ -87,6 +87,8 @@ def make_env(n, device, motion_file, synthetic):
     if not motion_file:
         raise SystemExit("give --motion_file (the task's motion yaml) or --synthetic")
     cfg["env"]["motion_file"] = motion_file
+    if motion_device:          # the motion library as a table on the device: fetch_amp_obs_demo is one launch (sim.mi355.amp_motion_device)
+        cfg["sim"].setdefault("mi355", {})["amp_motion_device"] = True
     return TocabiAMPLower(cfg, device, 0, True)
 
 
@@ -137,7 +139,7 @@ def train(args):
     tc = AD.load_train_yaml(args.train_yaml) if args.train_yaml else AD.TRAIN_CFG
     c, netc = tc["config"], tc["network"]
     dev = torch.device(args.device)
-    env = make_env(args.num_envs, args.device, args.motion_file, args.synthetic)
+    env = make_env(args.num_envs, args.device, args.motion_file, args.synthetic, args.motion_device)
     N, H, A = env.num_envs, int(c["horizon_length"]), env.num_actions
     lr0, lr_min, max_epochs = float(c["learning_rate"]), 1e-6, int(args.max_epochs or c["max_epochs"])
     if args.policy_backend == "hip":
@@ -297,6 +299,8 @@ def main():
     ap.add_argument("--max_epochs", type=int, default=0, help="of the learning-rate schedule (default: the yaml's)")
     ap.add_argument("--motion_file", default=None)
     ap.add_argument("--synthetic", action="store_true", help="the synthetic motion tables of tests/amp_motion_synth.py")
+    ap.add_argument("--motion-device", dest="motion_device", action="store_true",
+                    help="sim.mi355.amp_motion_device: the motion library on the device (demonstration fetches and reference starts without the host)")
     ap.add_argument("--train_yaml", default=None, help="cfg/train/TocabiAMPLowerPPO.yaml (default: the built-in copy of its values)")
     ap.add_argument("--backend", default="hip", choices=["hip", "torch"])
     ap.add_argument("--policy_backend", default="torch", choices=["torch", "hip"], help="the actor-critic: the inline torch loop or AmpActorCritic")

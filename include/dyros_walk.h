@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define DW_ABI_VERSION 10
+#define DW_ABI_VERSION 11
 
 /* ---- fixed sizes of the TOCABI model (reference: assets/mjcf/dyros_tocabi/xml/dyros_tocabi.xml) ---- */
 #define DW_NUM_BODIES   38   /* Gym rigid bodies, XML depth-first                         */
@@ -508,6 +508,59 @@ int dw_amp_reset_done(DwHandle *h, const DwAmpConfig *c, const DwAmpBuffers *b, 
  * (pinned host memory mapped to the device: the caller waits for an event recorded behind this launch and reads the number there, without a copy
  * of its own).  One launch; queue it BEFORE dw_amp_reset_done, which clears the flags.  ABI 10. */
 int dw_amp_reset_ids(const int64_t *reset_buf, int n, int64_t *ids, int64_t *count, int64_t *count_host, void *stream);
+
+
+/* ---- Row f-3, reference state initialisation on the device (ABI 11): the motion library of the AMP task (isaacgymdyros_amd/motion_lib.py;
+ * reference tasks/amp/utils_amp/tocabi_lower_motion_lib.py:61-154) as a table in device memory and kernels that do what get_motion_state,
+ * _reset_ref_state_init, _init_amp_obs and fetch_amp_obs_demo do (tasks/tocabi_amp_lower.py:105-131,144-305).  Bodies: csrc/dw_amp_motion.h.
+ * rows [total_rows, DW_MOTION_COLS] float32: columns 1..43 of the motions' tables one after the other (0..11 leg dof positions | 12..23 leg dof
+ * velocities | 24..26 root position | 27..30 root rotation xyzw | 31..33 root linear velocity | 34..36 root angular velocity | 37..42 the two foot
+ * positions), the three velocity groups already scaled by 0.0005 / dt of their motion; motion m = rows start[m] .. start[m] + num_frames[m] - 1;
+ * length [s], dt (signed: negative for a motion played backwards) and cum_weight (cumulative normalised weights) are float64. */
+#define DW_MOTION_COLS 43
+typedef struct DwMotionTable {
+    const float   *rows;
+    const int32_t *start, *num_frames;
+    const double  *length, *dt, *cum_weight;
+    int32_t num_motions, total_rows;
+} DwMotionTable;
+/* get_motion_state for n queries: frame pair and blend in float64 (phase = clip(t / length, 0, 1), i0 = trunc(phase (frames - 1)), blend =
+ * (t - i0 |dt|) / |dt| rounded to float32), root and key positions (1 - b) p0 + b p1 in float32 without contraction, the root rotation by the
+ * reference's slerp, the rest of frame i0.  motion_ids [n] int32, motion_times [n] float64 -> root_states [n,13] (position, rotation, linear,
+ * angular velocity), dof_pos / dof_vel [n,12], key_pos [n,2,3].  A time below zero extrapolates with a negative blend, as the reference does.
+ * validate_ids != 0: the ids are read back and checked on the host first (DW_EINVAL for one outside 0 .. num_motions - 1; the call waits for
+ * `stream`); 0: no host round trip, a row whose id is out of range is left unwritten. */
+int dw_amp_motion_state(const DwMotionTable *tab, int n, const int32_t *motion_ids, const double *motion_times, float *root_states, float *dof_pos,
+                        float *dof_vel, float *key_pos, int validate_ids, void *stream);
+/* The discriminator observations of `steps` motion frames per sample: out [n, steps, 34], slot k of sample i = dw_amp_disc_observations of the
+ * motion state at times0[i] + (-dt_policy (k + first_k)) (float64, in that order).  first_k = 0: fetch_amp_obs_demo (tasks/tocabi_amp_lower.py:
+ * 105-131); first_k = 1: the history of a reference start (_init_amp_obs, :258-305).  validate_ids as above. */
+int dw_amp_motion_obs(const DwMotionTable *tab, int n, int steps, const int32_t *motion_ids, const double *times0, double dt_policy, int first_k,
+                      int local_root_obs, float *out, int validate_ids, void *stream);
+/* dw_amp_reset_rows with the state initialisations Start / Random / Hybrid: per listed env a start kind (start_kind [n] int32: 0 default, 1 motion;
+ * NULL = all motion), a motion id and a time (motion_ids [n] int32, motion_times [n] float64; read for motion starts).  A motion start, in
+ * reset_idx's order: the legs' joint state from the motion (the upper body at its initial pose and at rest); the foot positions and the reset
+ * observation from the motion's root state and that joint state; then the INITIAL root state over the root row (tasks/amp/tocabi_amp_lower_base.py:
+ * 262-263: the reference's behaviour, kept); everything dw_amp_reset_rows does; the discriminator history: newest slot = the current
+ * observation, slot k = the motion's observation at time - dt_policy k.  Then the reference's history re-initialisation over two further id
+ * lists (its never-cleared _reset_default_env_ids / _reset_ref_env_ids, tasks/tocabi_amp_lower.py:258-267), in its order: every older slot of
+ * the envs hist_default_ids [n_hist_default] becomes their newest slot, then the older slots of hist_ref_ids [n_hist_ref] the observations of
+ * hist_ref_motion_ids / hist_ref_motion_times.  Either list may be NULL with a count of 0.  The motion ids are checked on the host (the call
+ * waits for `stream`; the caller's draws come from the host anyway).  dt_policy: the env's dt as float64 (DwAmpConfig.dt is its float32). */
+int dw_amp_reset_rows_motion(DwHandle *h, const DwAmpConfig *c, const DwAmpBuffers *b, const DwMotionTable *tab, const int64_t *ids, int n,
+                             const int32_t *start_kind, const int32_t *motion_ids, const double *motion_times, const float *power_scale_u,
+                             const float *rootvel_noise, const float *cmd_x_u, const float *cmd_y_u, const float *cmd_yaw_u, const float *qpos_bias_u,
+                             const float *quat_bias_u, const int64_t *perturb_timing, const int64_t *delay_idx, const int64_t *hist_default_ids,
+                             int n_hist_default, const int64_t *hist_ref_ids, int n_hist_ref, const int32_t *hist_ref_motion_ids,
+                             const double *hist_ref_motion_times, double dt_policy, void *stream);
+/* dw_amp_reset_done with the start drawn inside the kernel (DwAmpConfig.device_draws = 1 only; every draw is the kernel's).  state_init: 1 Start,
+ * 2 Random, 3 Hybrid.  Three more generator words per resetting env, block 0 of stream 15 under the key of the env's other reset draws (seed, env,
+ * draw counter): word 0 -> a reference start iff uniform < hybrid_init_prob (Hybrid only), word 1 -> the motion, the first m with uniform <
+ * cum_weight[m], word 2 -> time = float64(uniform) * length[m] (0 for Start); uniform = float32(word >> 8) 2^-24.  The discriminator history of the
+ * envs that reset, and of no others, is initialised (no torch twin, no stale id lists).  drawn_kind / drawn_motion [N] int32, drawn_time [N]
+ * float64: what was drawn, written for the envs that reset (each may be NULL). */
+int dw_amp_reset_done_motion(DwHandle *h, const DwAmpConfig *c, const DwAmpBuffers *b, const DwMotionTable *tab, int state_init,
+                             float hybrid_init_prob, double dt_policy, int32_t *drawn_kind, int32_t *drawn_motion, double *drawn_time, void *stream);
 
 
 #ifdef __cplusplus

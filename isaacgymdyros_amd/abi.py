@@ -25,9 +25,11 @@ EXPORTS = list(cbind.signatures("dyros_walk.h", "dw_"))
 # The fused TocabiAMPLower step (csrc/dw_amp_step.h) is carried by the HIP library and by the octet build of the host emulation
 # (tests/emul/), its one-launch form and dw_amp_reset_ids by the HIP library alone; the C oracle has neither, nor dw_terrain_log.
 _FUSED_AMP = ("amp_step_begin", "amp_step_mid", "amp_step_end", "amp_step", "amp_reset_rows", "amp_reset_done", "amp_reset_ids")
+# the device-resident motion library (csrc/dw_amp_motion.h): the HIP library alone
+_MOTION = ("amp_motion_state", "amp_motion_obs", "amp_reset_rows_motion", "amp_reset_done_motion")
 MAY_LACK = {"dw_": (),
-            "dwo_": _FUSED_AMP + ("terrain_log",),
-            "dwe_": _FUSED_AMP + ("step_obs", "amp_observations", "amp_disc_observations", "amp_reward", "amp_reset", "newwalk_reward",
+            "dwo_": _FUSED_AMP + _MOTION + ("terrain_log",),
+            "dwe_": _FUSED_AMP + _MOTION + ("step_obs", "amp_observations", "amp_disc_observations", "amp_reward", "amp_reset", "newwalk_reward",
                                   "body_positions")}
 
 

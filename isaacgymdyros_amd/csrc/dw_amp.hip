@@ -7,10 +7,13 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdio.h>
+#include <stdint.h>
+#include <vector>
 
 #include "dw_handle.h"
 #include "dw_amp.h"
 #include "dw_amp_step.h"
+#include "dw_amp_motion.h"
 
 extern "C" __attribute__((visibility("hidden"))) void dw_set_error(int code, const char *msg);          // dw_hip.hip: the thread's dw_last_error()
 
@@ -143,6 +146,127 @@ __global__ __launch_bounds__(1024) void dw_k_amp_reset_ids(const int64_t *__rest
         __syncthreads();          // (tab / pre / wtot are rewritten by the next sixteen chunks)
     }
     if (t == 0) { *count = base; if (count_host) *count_host = base; }
+}
+
+// ---- the motion library on the device (dw_amp_motion.h)
+// get_motion_state: one thread per (query, word group); the 40 threads of a query read neighbouring words of the same two table rows
+constexpr int MTPB = 256;
+__global__ __launch_bounds__(MTPB) void dw_k_amp_motion_state(const DwMotionTable T, int n, const int32_t *__restrict__ mids, const double *__restrict__ times,
+                                                              float *root_states, float *dof_pos, float *dof_vel, float *key_pos) {
+    const long long t = (long long)blockIdx.x * MTPB + threadIdx.x;
+    const long long i = t / dwa::MOTION_GROUPS;
+    if (i >= n) return;
+    const int g = (int)(t - i * dwa::MOTION_GROUPS), m = mids[i];
+    if (m < 0 || m >= T.num_motions) return;          // (ids come from device memory: never read past the table)
+    dwa::motion_group(T, m, times[i], g, root_states + 13 * (size_t)i, dof_pos + 12 * (size_t)i, dof_vel + 12 * (size_t)i, 1, key_pos + 6 * (size_t)i);
+}
+// The discriminator observation of `steps` motion frames per query: a workgroup takes MOI (query, slot) items; their states go to LDS by word group
+// over all threads, dw_amp_disc_observations' row function then runs with one thread per item, and the rows leave by word over all threads.
+// Row k of query i lands at out + ((row_slots * r + slot_off + k) * 34, r = i (dense: fetch_amp_obs_demo) or r = rows[i] (an env's history).
+constexpr int MOI = 32, MO_ST = 45, MO_OB = 35;          // (odd strides: thread = item access without bank conflicts)
+__global__ __launch_bounds__(MTPB) void dw_k_amp_motion_obs(const DwMotionTable T, int n, int steps, const int32_t *__restrict__ mids, const double *__restrict__ times0,
+                                                            double dt_policy, int first_k, int local_root_obs, const int64_t *__restrict__ rows, int num_rows,
+                                                            int row_slots, int slot_off, float *out) {
+    __shared__ float st[MOI][MO_ST], ob[MOI][MO_OB];
+    __shared__ int ok[MOI];
+    const long long item0 = (long long)blockIdx.x * MOI, items = (long long)n * steps;
+    const int tid = (int)threadIdx.x;
+    if (tid < MOI) {
+        const long long it = item0 + tid;
+        int v = 0;
+        if (it < items) {
+            const long long i = it / steps;
+            const int m = mids[i];
+            v = m >= 0 && m < T.num_motions;
+            if (rows) { const int64_t r = rows[i]; v = v && r >= 0 && r < num_rows; }
+        }
+        ok[tid] = v;
+    }
+    __syncthreads();
+    for (int w = tid; w < MOI * dwa::MOTION_GROUPS; w += MTPB) {
+        const int il = w / dwa::MOTION_GROUPS, g = w - il * dwa::MOTION_GROUPS;
+        if (!ok[il]) continue;
+        const long long it = item0 + il, i = it / steps;
+        const int k = (int)(it - i * steps);
+        float *s = st[il];
+        dwa::motion_group(T, mids[i], dwa::motion_slot_time(times0[i], dt_policy, k + first_k), g, s, s + 13, s + 25, 1, s + 37);
+    }
+    __syncthreads();
+    if (tid < MOI && ok[tid]) {
+        const float *s = st[tid];
+        dwa::disc_observations_row(s, s + 13, s + 25, 1, local_root_obs, s + 37, 2, ob[tid]);
+    }
+    __syncthreads();
+    for (int w = tid; w < MOI * dwa::AW; w += MTPB) {
+        const int il = w / dwa::AW, x = w - il * dwa::AW;
+        if (!ok[il]) continue;
+        const long long it = item0 + il, i = it / steps;
+        const int k = (int)(it - i * steps);
+        const size_t r = rows ? (size_t)rows[i] : (size_t)i;
+        out[((size_t)row_slots * r + (size_t)(slot_off + k)) * dwa::AW + x] = ob[il][x];
+    }
+}
+// the older slots of the listed envs' discriminator history become their newest slot (_init_amp_obs' default list, tasks/tocabi_amp_lower.py:258-272)
+__global__ __launch_bounds__(MTPB) void dw_k_amp_hist_default(const int64_t *__restrict__ ids, int n, int num_envs, int steps, float *amp_obs_buf) {
+    const int per = (steps - 1) * dwa::AW;
+    const long long t = (long long)blockIdx.x * MTPB + threadIdx.x;
+    const long long i = t / per;
+    if (i >= n) return;
+    const int w = (int)(t - i * per);
+    const int64_t e = ids[i];
+    if (e < 0 || e >= num_envs) return;
+    float *ab = amp_obs_buf + (size_t)steps * dwa::AW * (size_t)e;
+    ab[dwa::AW + w] = ab[w % dwa::AW];
+}
+__global__ __launch_bounds__(64 * RW) void dw_k_amp_reset_rows_motion(const dw::DevModel *__restrict__ M, const DwAmpConfig C, const DwAmpBuffers B, const dwa::GymRows G,
+                                                                     const int64_t *ids, int n, dwa::ResetSrc R, const dwa::ResetMotion RM) {
+    __shared__ dwa::StepLds S[RW];
+    const int w = (int)(threadIdx.x >> 6), k = (int)blockIdx.x * RW + w;
+    if (k >= n) return;                            // (wave-uniform)
+    const int e = (int)ids[k];
+    if (e < 0 || e >= C.num_envs) return;
+    R.row = (size_t)k;
+    dwa::reset_env_t<true>(dwa::EnvWave(), S[w], *M, C, B, G, R, RM, e);
+}
+__global__ __launch_bounds__(64 * RW) void dw_k_amp_reset_done_motion(const dw::DevModel *__restrict__ M, const DwAmpConfig C, const DwAmpBuffers B, const dwa::GymRows G,
+                                                                     dwa::ResetSrc R, const dwa::ResetMotion RM) {
+    __shared__ dwa::StepLds S[RW];
+    const int w = (int)(threadIdx.x >> 6), e = (int)blockIdx.x * RW + w;
+    if (e >= C.num_envs || B.reset_buf[e] == 0) return;          // (wave-uniform)
+    R.row = (size_t)e;
+    dwa::reset_env_t<true>(dwa::EnvWave(), S[w], *M, C, B, G, R, RM, e);
+}
+
+bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+const char *table_bad(const DwMotionTable *t) {
+    if (!t) return "null motion table";
+    if (!t->rows || !t->start || !t->num_frames || !t->length || !t->dt || !t->cum_weight) return "null pointer in the motion table";
+    if (!aligned(t->rows, 4) || !aligned(t->start, 4) || !aligned(t->num_frames, 4) || !aligned(t->length, 8) || !aligned(t->dt, 8) || !aligned(t->cum_weight, 8))
+        return "misaligned pointer in the motion table";
+    if (t->num_motions < 1 || t->total_rows < 1) return "empty motion table";
+    return nullptr;
+}
+// the motion ids of a caller-draws call, read back and checked on the host: 0 fine, DW_EINVAL one out of range, DW_EHIP the copy failed
+int motion_ids_bad(const int32_t *ids, int n, int num_motions, hipStream_t stream) {
+    if (n <= 0) return 0;
+    std::vector<int32_t> h((size_t)n);
+    if (hipMemcpyAsync(h.data(), ids, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return DW_EHIP;
+    }
+    for (int i = 0; i < n; ++i) if (h[(size_t)i] < 0 || h[(size_t)i] >= num_motions) return DW_EINVAL;
+    return 0;
+}
+int motion_ids_fail(const char *who, int rc) {
+    char m[200];
+    snprintf(m, sizeof m, rc == DW_EINVAL ? "%s: motion id out of range" : "%s: could not read the motion ids back", who);
+    return fail(rc, m);
+}
+void launch_motion_obs(const DwMotionTable &T, int n, int steps, const int32_t *mids, const double *times0, double dt_policy, int first_k, int local_root_obs,
+                       const int64_t *rows, int num_rows, int row_slots, int slot_off, float *out, hipStream_t stream) {
+    const long long items = (long long)n * steps;
+    hipLaunchKernelGGL(dw_k_amp_motion_obs, dim3((unsigned)((items + MOI - 1) / MOI)), dim3(MTPB), 0, stream, T, n, steps, mids, times0, dt_policy, first_k,
+                       local_root_obs, rows, num_rows, row_slots, slot_off, out);
 }
 
 bool amp_args_ok(const DwAmpConfig *c, const DwAmpBuffers *b) {
@@ -360,6 +484,99 @@ int dw_amp_reset_done(DwHandle *h, const DwAmpConfig *c, const DwAmpBuffers *b, 
                     d->delay_idx, d->rootvel_noise, 0, true, c->randomize != 0};
     hipLaunchKernelGGL(dw_k_amp_reset_done, dim3((c->num_envs + RW - 1) / RW), dim3(64 * RW), 0, (hipStream_t)stream, h->d_model, *c, *b, gym_rows(h), R);
     return launched("dw_amp_reset_done: launch");
+}
+
+int dw_amp_motion_state(const DwMotionTable *tab, int n, const int32_t *motion_ids, const double *motion_times, float *root_states, float *dof_pos,
+                        float *dof_vel, float *key_pos, int validate_ids, void *stream) {
+    if (const char *m = table_bad(tab)) { char t[160]; snprintf(t, sizeof t, "dw_amp_motion_state: %s", m); return fail(DW_EINVAL, t); }
+    if (n < 0 || (long long)n * dwa::MOTION_GROUPS > 0x7fffffffll * MTPB) return fail(DW_EINVAL, "dw_amp_motion_state: n out of range");
+    if (!motion_ids || !motion_times || !root_states || !dof_pos || !dof_vel || !key_pos) return fail(DW_EINVAL, "dw_amp_motion_state: null argument");
+    if (!aligned(motion_ids, 4) || !aligned(motion_times, 8) || !aligned(root_states, 4) || !aligned(dof_pos, 4) || !aligned(dof_vel, 4) || !aligned(key_pos, 4))
+        return fail(DW_EINVAL, "dw_amp_motion_state: misaligned argument");
+    if (n == 0) return DW_OK;
+    if (validate_ids) if (const int rc = motion_ids_bad(motion_ids, n, tab->num_motions, (hipStream_t)stream)) return motion_ids_fail("dw_amp_motion_state", rc);
+    const long long threads = (long long)n * dwa::MOTION_GROUPS;
+    hipLaunchKernelGGL(dw_k_amp_motion_state, dim3((unsigned)((threads + MTPB - 1) / MTPB)), dim3(MTPB), 0, (hipStream_t)stream, *tab, n, motion_ids, motion_times,
+                       root_states, dof_pos, dof_vel, key_pos);
+    return launched("dw_amp_motion_state: launch");
+}
+
+int dw_amp_motion_obs(const DwMotionTable *tab, int n, int steps, const int32_t *motion_ids, const double *times0, double dt_policy, int first_k,
+                      int local_root_obs, float *out, int validate_ids, void *stream) {
+    if (const char *m = table_bad(tab)) { char t[160]; snprintf(t, sizeof t, "dw_amp_motion_obs: %s", m); return fail(DW_EINVAL, t); }
+    if (n < 0 || steps < 1 || first_k < 0 || (long long)n * steps > 0x7fffffffll * MOI) return fail(DW_EINVAL, "dw_amp_motion_obs: n < 0, steps < 1, first_k < 0 or too many rows");
+    if (!motion_ids || !times0 || !out) return fail(DW_EINVAL, "dw_amp_motion_obs: null argument");
+    if (!aligned(motion_ids, 4) || !aligned(times0, 8) || !aligned(out, 4)) return fail(DW_EINVAL, "dw_amp_motion_obs: misaligned argument");
+    if (n == 0) return DW_OK;
+    if (validate_ids) if (const int rc = motion_ids_bad(motion_ids, n, tab->num_motions, (hipStream_t)stream)) return motion_ids_fail("dw_amp_motion_obs", rc);
+    launch_motion_obs(*tab, n, steps, motion_ids, times0, dt_policy, first_k, local_root_obs, nullptr, 0, steps, 0, out, (hipStream_t)stream);
+    return launched("dw_amp_motion_obs: launch");
+}
+
+int dw_amp_reset_rows_motion(DwHandle *h, const DwAmpConfig *c, const DwAmpBuffers *b, const DwMotionTable *tab, const int64_t *ids, int n,
+                             const int32_t *start_kind, const int32_t *motion_ids, const double *motion_times, const float *power_scale,
+                             const float *rootvel_noise, const float *cmd_x, const float *cmd_y, const float *cmd_yaw, const float *qpos_bias,
+                             const float *quat_bias, const int64_t *perturb_timing, const int64_t *delay_idx, const int64_t *hist_default_ids,
+                             int n_hist_default, const int64_t *hist_ref_ids, int n_hist_ref, const int32_t *hist_ref_motion_ids,
+                             const double *hist_ref_motion_times, double dt_policy, void *stream) {
+    if (!h || !amp_args_ok(c, b) || !ids || !rootvel_noise || !cmd_x || !cmd_y || !cmd_yaw || !perturb_timing || !delay_idx || !motion_ids || !motion_times)
+        return fail(DW_EINVAL, "dw_amp_reset_rows_motion: bad configuration or null argument");
+    if (const char *m = table_bad(tab)) { char t[160]; snprintf(t, sizeof t, "dw_amp_reset_rows_motion: %s", m); return fail(DW_EINVAL, t); }
+    if (c->noise && (!qpos_bias || !quat_bias)) return fail(DW_EINVAL, "dw_amp_reset_rows_motion: noise needs the bias draws");
+    if (!b->epi_len_log || !b->perturbation_count || !b->perturb_timing || !b->pert_on || !b->initial_root_states)
+        return fail(DW_EINVAL, "dw_amp_reset_rows_motion: the reset's own buffers are missing from DwAmpBuffers");
+    if (!h->bound) return fail(DW_ESTATE, "dw_amp_reset_rows_motion: dw_bind first");
+    if (n < 0 || n > c->num_envs || c->num_envs != h->cfg.num_envs) return fail(DW_EINVAL, "dw_amp_reset_rows_motion: n out of range or num_envs differs from the handle's");
+    if (n_hist_default < 0 || n_hist_ref < 0 || n_hist_default > c->num_envs || n_hist_ref > c->num_envs || (n_hist_default > 0 && !hist_default_ids) ||
+        (n_hist_ref > 0 && (!hist_ref_ids || !hist_ref_motion_ids || !hist_ref_motion_times)))
+        return fail(DW_EINVAL, "dw_amp_reset_rows_motion: a history list is missing or its count is out of range");
+    if (!aligned(ids, 8) || !aligned(motion_ids, 4) || !aligned(motion_times, 8) || (start_kind && !aligned(start_kind, 4)) || !aligned(hist_default_ids, 8) ||
+        !aligned(hist_ref_ids, 8) || !aligned(hist_ref_motion_ids, 4) || !aligned(hist_ref_motion_times, 8))
+        return fail(DW_EINVAL, "dw_amp_reset_rows_motion: misaligned argument");
+    const hipStream_t st = (hipStream_t)stream;
+    if (const int rc = motion_ids_bad(motion_ids, n, tab->num_motions, st)) return motion_ids_fail("dw_amp_reset_rows_motion", rc);
+    if (const int rc = motion_ids_bad(hist_ref_motion_ids, n_hist_ref, tab->num_motions, st)) return motion_ids_fail("dw_amp_reset_rows_motion (history list)", rc);
+    if (n > 0) {
+        DwAmpConfig cc = *c;
+        cc.device_draws = 0;                           // (every draw of this entry point is the caller's)
+        dwa::ResetSrc R{power_scale, cmd_x, cmd_y, cmd_yaw, qpos_bias, quat_bias, nullptr, nullptr, perturb_timing, delay_idx, rootvel_noise, 0, false,
+                        power_scale != nullptr};
+        const dwa::ResetMotion RM{*tab, start_kind, motion_ids, motion_times, 0, 0.0f, dt_policy, nullptr, nullptr, nullptr};
+        hipLaunchKernelGGL(dw_k_amp_reset_rows_motion, dim3((n + RW - 1) / RW), dim3(64 * RW), 0, st, h->d_model, cc, *b, gym_rows(h), ids, n, R, RM);
+        if (const int rc = launched("dw_amp_reset_rows_motion: launch")) return rc;
+    }
+    // the reference's history re-initialisation over its two lists, default first (tasks/tocabi_amp_lower.py:258-267)
+    if (c->amp_steps > 1 && n_hist_default > 0) {
+        const long long threads = (long long)n_hist_default * (c->amp_steps - 1) * dwa::AW;
+        hipLaunchKernelGGL(dw_k_amp_hist_default, dim3((unsigned)((threads + MTPB - 1) / MTPB)), dim3(MTPB), 0, st, hist_default_ids, n_hist_default, c->num_envs,
+                           c->amp_steps, b->amp_obs_buf);
+        if (const int rc = launched("dw_amp_reset_rows_motion: history launch")) return rc;
+    }
+    if (c->amp_steps > 1 && n_hist_ref > 0) {
+        launch_motion_obs(*tab, n_hist_ref, c->amp_steps - 1, hist_ref_motion_ids, hist_ref_motion_times, dt_policy, 1, c->local_root_obs, hist_ref_ids, c->num_envs,
+                          c->amp_steps, 1, b->amp_obs_buf, st);
+        if (const int rc = launched("dw_amp_reset_rows_motion: history launch")) return rc;
+    }
+    return DW_OK;
+}
+
+int dw_amp_reset_done_motion(DwHandle *h, const DwAmpConfig *c, const DwAmpBuffers *b, const DwMotionTable *tab, int state_init, float hybrid_init_prob,
+                             double dt_policy, int32_t *drawn_kind, int32_t *drawn_motion, double *drawn_time, void *stream) {
+    if (!amp_args_ok(c, b)) return fail(DW_EINVAL, "dw_amp_reset_done_motion: bad configuration or null argument");
+    if (const char *m = handle_ok(h, c)) { char t[160]; snprintf(t, sizeof t, "dw_amp_reset_done_motion: %s", m); return fail(h && !h->bound ? DW_ESTATE : DW_EINVAL, t); }
+    if (const char *m = table_bad(tab)) { char t[160]; snprintf(t, sizeof t, "dw_amp_reset_done_motion: %s", m); return fail(DW_EINVAL, t); }
+    if (!c->device_draws) return fail(DW_EINVAL, "dw_amp_reset_done_motion: the start is drawn in the kernel: device_draws only (dw_amp_reset_rows_motion takes the caller's)");
+    if (state_init < 1 || state_init > 3) return fail(DW_EINVAL, "dw_amp_reset_done_motion: state_init must be 1 (Start), 2 (Random) or 3 (Hybrid)");
+    if (!b->epi_len_log || !b->perturbation_count || !b->perturb_timing || !b->pert_on || !b->initial_root_states)
+        return fail(DW_EINVAL, "dw_amp_reset_done_motion: the reset's own buffers are missing from DwAmpBuffers");
+    if ((c->dr_damping || c->dr_armature) && (!b->nominal_damping || !b->nominal_armature || c->dr_frequency < 0))
+        return fail(DW_EINVAL, "dw_amp_reset_done_motion: dof-property randomisation needs the nominal tables");
+    if (c->delay_idx_range[1] <= c->delay_idx_range[0]) return fail(DW_EINVAL, "dw_amp_reset_done_motion: delay_idx_range is empty");
+    if (!aligned(drawn_kind, 4) || !aligned(drawn_motion, 4) || !aligned(drawn_time, 8)) return fail(DW_EINVAL, "dw_amp_reset_done_motion: misaligned argument");
+    dwa::ResetSrc R{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, true, c->randomize != 0};
+    const dwa::ResetMotion RM{*tab, nullptr, nullptr, nullptr, state_init, hybrid_init_prob, dt_policy, drawn_kind, drawn_motion, drawn_time};
+    hipLaunchKernelGGL(dw_k_amp_reset_done_motion, dim3((c->num_envs + RW - 1) / RW), dim3(64 * RW), 0, (hipStream_t)stream, h->d_model, *c, *b, gym_rows(h), R, RM);
+    return launched("dw_amp_reset_done_motion: launch");
 }
 
 }  // extern "C"

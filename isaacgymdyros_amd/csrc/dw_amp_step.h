@@ -25,6 +25,7 @@
 #pragma once
 
 #include "dw_amp.h"
+#include "dw_amp_motion.h"
 
 #if defined(__clang__)
 #pragma clang fp contract(off)
@@ -77,7 +78,7 @@ struct GymRows { float *root_states, *dof_state, *contact_forces, *dof_damping, 
 
 // ---------------------------------------------------------------------------------------------------------------------- draws
 struct DrawKey { unsigned long long seed; unsigned int env; unsigned long long ctr; };
-enum { DS_RAMP = 1, DS_ENC = 2 /* + substep, < 8 */, DS_ROOTVEL = 12, DS_RESET = 13, DS_DR = 14 };
+enum { DS_RAMP = 1, DS_ENC = 2 /* + substep, < 8 */, DS_ROOTVEL = 12, DS_RESET = 13, DS_DR = 14, DS_MOTION = 15 /* the start of a resetting env: dw_amp_motion.h motion_draw */ };
 DW_HD void draw_block(const DrawKey &k, unsigned int stream, unsigned int idx, unsigned int *c) {
     c[0] = idx; c[1] = k.env; c[2] = (unsigned int)k.ctr; c[3] = ((unsigned int)(k.ctr >> 32) & 0x0fffffffu) | (stream << 28);
     dw::philox4x32_10(c, (unsigned int)k.seed, (unsigned int)(k.seed >> 32));
@@ -653,10 +654,48 @@ struct ResetSrc {
     bool power;                          // draw power_scale
 };
 
-// reset_idx of env e (tasks/amp/tocabi_amp_lower_base.py:238-305 with the default state initialisation, then
-// tasks/tocabi_amp_lower.py:144-147,258-272)
-DW_HD void reset_env(const EnvWave &W, StepLds &S, const dw::DevModel &M, const DwAmpConfig &C, const DwAmpBuffers &B, const GymRows &G,
-                     const ResetSrc &R, int e) {
+// Where a reset env's START comes from under the state initialisations Start / Random / Hybrid (dw_amp_reset_rows_motion: the caller's kind,
+// motion and time, rows at ResetSrc::row; dw_amp_reset_done_motion: drawn here, stream DS_MOTION of the env's reset key).
+struct ResetMotion {
+    DwMotionTable T;
+    const int32_t *kind, *motion;          // caller's: kind NULL = every listed env starts from its motion
+    const double *time;
+    int state_init;                        // drawn here (kind, motion, time all NULL): 1 Start, 2 Random, 3 Hybrid
+    float hybrid_prob;
+    double dt_policy;
+    int32_t *drawn_kind, *drawn_motion;    // [N] by env, what this reset used (each may be NULL)
+    double *drawn_time;
+};
+
+// reset_idx of env e (tasks/amp/tocabi_amp_lower_base.py:238-305, then tasks/tocabi_amp_lower.py:144-147,258-272).  MOTION = false: the default
+// state initialisation.  MOTION = true: the env starts as RM says -- for a motion start (tasks/tocabi_amp_lower.py:180-256) the legs' joint state
+// is the motion's, the foot positions and the reset observation are computed from the MOTION's root state and that joint state, the root row gets
+// the INITIAL root state all the same (tasks/amp/tocabi_amp_lower_base.py:262-263 writes it over what _reset_actors set: the reference's
+// behaviour, kept), the encoder state is the initial pose's, and the discriminator history is the current observation followed by the motion's
+// observations at time - dt k.  S.cf (unused by the default reset) carries the motion's root state [0,13), one history slot's state [32,75)
+// and observation [80,114).
+template <bool MOTION>
+DW_HD void reset_env_t(const EnvWave &W, StepLds &S, const dw::DevModel &M, const DwAmpConfig &C, const DwAmpBuffers &B, const GymRows &G,
+                       const ResetSrc &R, const ResetMotion &RM, int e) {
+    enum { MO_ROOT = 0, MO_SLOT = 32, MO_OUT = 80 };
+    static_assert(MO_OUT + AW <= DW_NUM_BODIES * 3 && MO_SLOT + 43 <= MO_OUT, "the motion start's rows fit StepLds::cf");
+    // the env's start, the same in every lane (each lane works it out for itself: no value crosses a lane inside a region)
+    auto start_of = [&](unsigned long long ctr) -> MotionDraw {
+        MotionDraw d; d.kind = 0; d.motion = 0; d.time = 0.0;
+        if constexpr (MOTION) {
+            if (RM.motion) {
+                d.kind = RM.kind ? (RM.kind[R.row] != 0 ? 1 : 0) : 1;
+                d.motion = RM.motion[R.row]; d.time = RM.time[R.row];
+                if (d.motion < 0 || d.motion >= RM.T.num_motions) { d.kind = 0; d.motion = 0; }          // (ids come from device memory: never read past the table)
+            } else {
+                DrawKey k; k.seed = C.seed; k.env = (unsigned int)e; k.ctr = ctr;
+                unsigned int c4[4];
+                draw_block(k, DS_MOTION, 0u, c4);
+                d = motion_draw(RM.T, c4, RM.state_init, RM.hybrid_prob);
+            }
+        }
+        return d;
+    };
     // Five regions (six until round 6, each ending in a drain of the wave's outstanding memory operations): (1) EVERY global read of the
     // reset -- the leg model, the old episode's last readings, the action-history words the reset observation shows, counters -- and every
     // generator block the reset draws from, one per lane; (2) the stores that depend on nothing else; (3) the serial functions and the stores
@@ -672,6 +711,7 @@ DW_HD void reset_env(const EnvWave &W, StepLds &S, const dw::DevModel &M, const 
         // ---- requests
         const unsigned long long ctr = dev ? (unsigned long long)B.draw_ctr[e] : 0ull;
         const int ah_head = C.hist_ring ? B.hist_head[2 * (size_t)e] : 0;
+        const MotionDraw st = start_of(ctr);
         float qn = 0.0f, qv = 0.0f, bias = 0.0f, qb = 0.0f, cmd = 0.0f, nzs = 0.0f, root = 0.0f, q0 = 0.0f, epi = 0.0f;
         if (l < 12) { qn = B.qpos_noise[(size_t)DW_NUM_DOF * e + l]; qv = B.qvel_noise[(size_t)DW_NUM_DOF * e + l]; bias = B.qpos_bias[12 * (size_t)e + l]; }
         if (l < 3) { qb = B.quat_bias[3 * (size_t)e + l]; cmd = B.commands[3 * (size_t)e + l]; }
@@ -704,18 +744,31 @@ DW_HD void reset_env(const EnvWave &W, StepLds &S, const dw::DevModel &M, const 
         // ---- what the reset observation is made of: the episode's LAST encoder reading, biases and command (the reference computes it
         //      before it draws the new ones, :253 before :266-279)
         if (l == 0) { S.i64[0] = (long long)ctr; S.touch = drr ? 1 : 0; }
+        if constexpr (MOTION) {
+            if (l == 0) {
+                S.i64[1] = st.kind; S.i64[2] = st.motion;
+                __builtin_memcpy(&S.i64[3], &st.time, sizeof(double));
+                if (RM.drawn_kind) RM.drawn_kind[e] = st.kind;
+                if (RM.drawn_motion) RM.drawn_motion[e] = st.kind ? st.motion : -1;
+                if (RM.drawn_time) RM.drawn_time[e] = st.kind ? st.time : 0.0;
+            }
+        }
         if (l < 12) { S.small[SO_QN + l] = qn; S.small[SO_QV + l] = qv; S.small[SO_BIAS + l] = bias; }
         if (l < 3) { S.small[SO_QB + l] = qb; S.small[SO_CMD + l] = cmd; }
         if (l < 6) S.small[SO_NZ + l] = nzs;
         if (l == 63) S.small[SO_EPI] = epi;
         if (l < 13) S.root[l] = root;
-        if (l < DW_NUM_DOF) { S.ds[2 * l] = q0; S.ds[2 * l + 1] = 0.0f; }
+        if (l < DW_NUM_DOF && !(st.kind && l < 12)) { S.ds[2 * l] = q0; S.ds[2 * l + 1] = 0.0f; }
+        if constexpr (MOTION) {
+            // a motion start: the legs from the motion, the upper body at its initial pose and at rest (tasks/tocabi_amp_lower.py:214-215)
+            if (st.kind && l < MOTION_GROUPS) motion_group(RM.T, st.motion, st.time, l, S.cf + MO_ROOT, S.ds, S.ds + 1, 2, S.cf + MO_ROOT + 13);
+        }
     });
     W.par([&](int l) DWA_INL {
         if (l < 6 && !R.rootvel_noise) S.small[SO_NZ + l] = (C.noise && dev) ? u32_uniform(word(DS_RESET, 40 + l)) * 0.05f - 0.025f : 0.0f;
         // the Gym tensors' rows: initial root state, initial pose at rest, no contact (_reset_actors, :611-626)
         if (l < 13) G.root_states[13 * (size_t)e + l] = S.root[l];
-        if (l < DW_NUM_DOF) { G.dof_state[((size_t)DW_NUM_DOF * e + l) * 2] = S.ds[2 * l]; G.dof_state[((size_t)DW_NUM_DOF * e + l) * 2 + 1] = 0.0f; }
+        if (l < DW_NUM_DOF) { G.dof_state[((size_t)DW_NUM_DOF * e + l) * 2] = S.ds[2 * l]; G.dof_state[((size_t)DW_NUM_DOF * e + l) * 2 + 1] = MOTION ? S.ds[2 * l + 1] : 0.0f; }
         for (int i = l; i < DW_NUM_BODIES * 3; i += 64) G.contact_forces[(size_t)DW_NUM_BODIES * 3 * e + i] = 0.0f;
         // (the draws arrive as raw uniforms; the values are formed with torch's arithmetic: `(hi - lo) * u + lo` with the scalars
         //  rounded to float32 first, `x / s` as a multiplication by 1.0f / s on a GPU and a division on a CPU)
@@ -738,7 +791,10 @@ DW_HD void reset_env(const EnvWave &W, StepLds &S, const dw::DevModel &M, const 
         }
     });
     W.par([&](int l) DWA_INL {
-        const float *r = S.root, *ds = S.ds;
+        // (a motion start: the rigid-body rows and the reset observation see the MOTION's root state -- the reference refreshes and observes
+        //  before it writes the initial root state over the row, :253 before :262-263)
+        const bool mstart = MOTION && S.i64[1] != 0;
+        const float *r = mstart ? S.cf + MO_ROOT : S.root, *ds = S.ds;
         if (l < 2) {          // the rigid-body rows of the new state
             float p[3];
             body_position(S.LM, r, ds, 0, l == 0 ? 6 : 12, p);
@@ -759,7 +815,7 @@ DW_HD void reset_env(const EnvWave &W, StepLds &S, const dw::DevModel &M, const 
         for (int i = l; i < C.log_slots * 12; i += 64) B.action_log[(size_t)C.log_slots * 12 * e + i] = 0.0f;
         if (l < DW_NUM_DOF) {
             const size_t g = (size_t)DW_NUM_DOF * e + l;
-            const float q0 = S.ds[2 * l];
+            const float q0 = mstart ? B.init_angle[l] : S.ds[2 * l];          // (the encoder state restarts from the INITIAL pose, :266-268)
             B.dof_vel_pre[g] = 0.0f; B.qpos_noise[g] = q0; B.qpos_pre[g] = q0; B.qvel_noise[g] = 0.0f;
         }
         if (l < 12) {
@@ -810,10 +866,36 @@ DW_HD void reset_env(const EnvWave &W, StepLds &S, const dw::DevModel &M, const 
     W.par([&](int l) DWA_INL {
         // discriminator history of a default start: every slot the current observation (tasks/tocabi_amp_lower.py:258-272)
         float *ab = B.amp_obs_buf + (size_t)C.amp_steps * AW * e;
-        for (int i = l; i < C.amp_steps * AW; i += 64) ab[i] = S.amp[i % AW];
+        const bool mstart = MOTION && S.i64[1] != 0;
+        for (int i = l; i < (mstart ? 1 : C.amp_steps) * AW; i += 64) ab[i] = S.amp[i % AW];
         if (l < AW) B.amp_obs1[(size_t)AW * e + l] = S.amp[l];
         if (dev && l == 0) B.draw_ctr[e] = (long long)((unsigned long long)S.i64[0] + 1ull);
     });
+    if constexpr (MOTION) {
+        // discriminator history of a motion start (tasks/tocabi_amp_lower.py:292-305): slot k = the motion's observation at time - dt k.  One slot
+        // at a time: its state by 40 lanes, its observation by one, its 34 words by 34.  (S.i64[1] is the same in every lane: wave-uniform.)
+        if (S.i64[1] != 0) {
+            for (int k = 1; k < C.amp_steps; ++k) {
+                W.par([&](int l) DWA_INL {
+                    double t0;
+                    __builtin_memcpy(&t0, &S.i64[3], sizeof(double));
+                    float *st = S.cf + MO_SLOT;
+                    if (l < MOTION_GROUPS) motion_group(RM.T, (int)S.i64[2], motion_slot_time(t0, RM.dt_policy, k), l, st, st + 13, st + 25, 1, st + 37);
+                });
+                W.par([&](int l) DWA_INL {
+                    const float *st = S.cf + MO_SLOT;
+                    if (l == 0) disc_observations_row(st, st + 13, st + 25, 1, C.local_root_obs, st + 37, 2, S.cf + MO_OUT);
+                });
+                W.par([&](int l) DWA_INL {
+                    if (l < AW) B.amp_obs_buf[((size_t)C.amp_steps * e + k) * AW + l] = S.cf[MO_OUT + l];
+                });
+            }
+        }
+    }
+}
+DW_HD void reset_env(const EnvWave &W, StepLds &S, const dw::DevModel &M, const DwAmpConfig &C, const DwAmpBuffers &B, const GymRows &G,
+                     const ResetSrc &R, int e) {
+    reset_env_t<false>(W, S, M, C, B, G, R, ResetMotion{}, e);
 }
 
 }  // namespace dwa

@@ -53,6 +53,33 @@ def slerp(q0: torch.Tensor, q1: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
     return torch.where(torch.abs(c) >= 1, q0, q)
 
 
+DEVICE_TABLE_COLS = 43                 # a row of the device table: columns 1..43 of a motion table (the time column is not kept)
+
+
+class MotionDeviceTable:
+    """What TocabiLowerMotionLib.device_table() returns: the tensors of include/dyros_walk.h's DwMotionTable on one device.  They are
+    kept alive by this object; struct() is the table of their addresses."""
+
+    def __init__(self, rows, start, num_frames, length, dt, cum_weight):
+        self.rows, self.start, self.num_frames, self.length, self.dt, self.cum_weight = rows, start, num_frames, length, dt, cum_weight
+        self._struct = None
+
+    def num_motions(self) -> int:
+        return int(self.start.shape[0])
+
+    def struct(self):
+        if self._struct is None:
+            from . import abi
+            t = abi.DwMotionTable()
+            for name in ("rows", "start", "num_frames", "length", "dt", "cum_weight"):
+                v = getattr(self, name)
+                assert v.is_contiguous()
+                setattr(t, name, v.data_ptr())
+            t.num_motions, t.total_rows = self.num_motions(), int(self.rows.shape[0])
+            self._struct = t
+        return self._struct
+
+
 class TocabiLowerMotionLib:
 
     def __init__(self, motion_file: str, num_dofs: int, device):
@@ -154,3 +181,26 @@ class TocabiLowerMotionLib:
         be = b.unsqueeze(-1)
         key_pos = (1.0 - be) * dev(r0[:, COL_KEY].reshape(-1, 2, 3)) + be * dev(r1[:, COL_KEY].reshape(-1, 2, 3))
         return root_pos, root_rot, root_vel, root_ang, dof_pos, dof_vel, key_pos
+
+    # ------------------------------------------------------------------ the same table, resident on the device
+    def device_table(self, device=None) -> MotionDeviceTable:
+        """The motion table as the HIP kernels read it (include/dyros_walk.h DwMotionTable; csrc/dw_amp_motion.h), uploaded once:
+        rows [total_rows, 43] float32 = columns 1..43 of the float64 table -- positions and quaternions rounded once to float32, the
+        three velocity groups pre-scaled per motion as `v * 0.0005 / dt` (left to right in float64, then rounded) -- and per motion
+        start / num_frames (int32), length, the SIGNED dt and the cumulative weights (float64).
+
+        Rounding the table once gives the bits get_motion_state's per-query dev() rounding gives: both are elementwise -- a gathered
+        row rounded is the rounded row gathered, and the velocity scale depends on the row's motion only -- so frame pair and blend
+        (float64, from length / dt / num_frames) then the float32 blends on this table reproduce get_motion_state bit for bit
+        (tests/test_amp_motion_device.py).  The host table and the numpy sampling above stay as they are."""
+        device = self._device if device is None else device
+        t = self._table[:, 1:1 + DEVICE_TABLE_COLS].copy()
+        dt_row = np.repeat(self._motion_dt, self._motion_num_frames)[:, np.newaxis]
+        for col in (COL_QVEL, COL_RVEL, COL_RANG):
+            c = slice(col.start - 1, col.stop - 1)
+            t[:, c] = t[:, c] * FRAME_DT / dt_row
+        def up(a, dtype):
+            return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device=device)
+        return MotionDeviceTable(up(t, torch.float), up(self._start, torch.int32), up(self._motion_num_frames, torch.int32),
+                                 up(self._motion_lengths, torch.float64), up(self._motion_dt, torch.float64),
+                                 up(np.cumsum(self._motion_weights), torch.float64))

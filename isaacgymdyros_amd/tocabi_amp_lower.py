@@ -292,7 +292,14 @@ class TocabiAMPLower(VecTask):
         # torch path -- stateInit Start / Random / Hybrid, or amp_fused_reset off -- reads the histories in the reference's shifting
         # layout (_compute_observations(env_ids)), so the rings default to ON only where every reset is the fused one, and asking
         # for them elsewhere is an error rather than a silently rotated observation.
-        ring_ok = self._fused and self._fused_reset and self._state_init == "Default"
+        # cfg sim.mi355.amp_motion_device (default off): the motion library as a table on the device (motion_lib.device_table, csrc/dw_amp_motion.h).
+        # The fused reset then covers stateInit Start / Random / Hybrid as well (dw_amp_reset_rows_motion with the caller's draws -- torch's
+        # generator and numpy's, in the torch path's order, so the two paths agree -- or dw_amp_reset_done_motion with amp_device_draws), and
+        # fetch_amp_obs_demo is one launch (dw_amp_motion_obs).  Off: every path below is as it was.
+        self._motion_device = bool(mi.get("amp_motion_device", False))
+        self._motion_tab = self._motion_lib.device_table(dev) if (self._motion_device and self._motion_lib is not None) else None
+        every_reset_fused = self._state_init == "Default" or self._motion_device
+        ring_ok = self._fused and self._fused_reset and every_reset_fused
         if "amp_hist_ring" in mi and bool(mi["amp_hist_ring"]) and not ring_ok:
             raise ValueError("sim.mi355.amp_hist_ring needs amp_fused with the fused reset (amp_fused_reset, stateInit 'Default'): "
                              "the torch reset path reads the histories in the reference's shifting layout")
@@ -300,7 +307,7 @@ class TocabiAMPLower(VecTask):
         self._device_draws = bool(mi.get("amp_device_draws", False))
         if self._device_draws and not (self._fused and self._fused_reset):
             raise ValueError("sim.mi355.amp_device_draws needs amp_fused (step and reset)")
-        if self._device_draws and self._state_init != "Default":
+        if self._device_draws and not every_reset_fused:
             raise ValueError("sim.mi355.amp_device_draws: the fused reset covers stateInit 'Default' only")
         # cfg sim.mi355.amp_one_launch (fused step on the plane; default OFF): the whole step -- the three task kernels and the K physics substeps
         # between them -- as ONE launch (dw_amp_step, include/dyros_walk.h): same arithmetic in the same order, same bits
@@ -323,6 +330,9 @@ class TocabiAMPLower(VecTask):
         self._amp_obs1 = torch.zeros(N, NUM_AMP_OBS_PER_STEP, **f)
         self._reset_default_env_ids, self._reset_ref_env_ids = [], []
         self._reset_ref_motion_ids = self._reset_ref_motion_times = None
+        self._reset_ref_dev = None          # (amp_motion_device: the two arrays above on the device, int32 / float64)
+        self._drawn_start = None            # (amp_motion_device with amp_device_draws: what dw_amp_reset_done_motion drew, by env)
+        self._demo_gen = None
         if self._pd_control:
             lo, hi = self._phys.model.dof_lower, self._phys.model.dof_upper
             lo, hi = np.minimum(lo, hi), np.maximum(lo, hi)
@@ -369,7 +379,7 @@ class TocabiAMPLower(VecTask):
         n = len(env_ids)
         if n == 0:
             return
-        if self._fused_reset and self._state_init == "Default":
+        if self._fused_reset and (self._state_init == "Default" or self._motion_device):
             return self._reset_fused(env_ids)
         if self.randomize:
             self.power_scale[env_ids] = self._rand_float(0.8, 1.2, (n, 12))
@@ -438,6 +448,9 @@ class TocabiAMPLower(VecTask):
         if self.randomize:
             ps = self._rand(n, 12)
             self._randomize_dof_properties(env_ids)
+        motion = self._state_init != "Default"
+        if motion:
+            kind, mids, times = self._draw_starts(env_ids)          # (_reset_actors' draws, where _reset_actors makes them)
         self.time_step += 1
         nz = self._rand(N, 6) * 0.05 - 0.025 if self.noise else torch.zeros(N, 6, device=self._tdev)
         cx, cy, cyaw = self._rand(n), self._rand(n), self._rand(n)
@@ -447,10 +460,52 @@ class TocabiAMPLower(VecTask):
         ptime = self._rng.randint(0, int(8 / 0.002), (n,))
         didx = self._rng.randint(1 + int(0.002 / self.dt), 1 + round(0.01 / self.dt), (n,))
         c, b = self._fused_tables()
+        if motion:
+            # the history re-initialisation runs over the reference's never-cleared id lists (_reset_actors' comment), as _init_amp_obs does
+            hd, hr = self._reset_default_env_ids, self._reset_ref_env_ids
+            hd = hd.contiguous() if len(hd) > 0 else None
+            hr = hr.contiguous() if len(hr) > 0 else None
+            hm, ht = self._reset_ref_dev if hr is not None else (None, None)
+            self._chk(self._api["amp_reset_rows_motion"](
+                self._phys._h, C.byref(c), C.byref(b), C.byref(self._motion_tab.struct()), _p(env_ids.contiguous()), n, _p(kind), _p(mids), _p(times),
+                _p(ps), _p(nz), _p(cx), _p(cy), _p(cyaw), _p(qb), _p(quatb), _p(ptime), _p(didx), _p(hd), 0 if hd is None else len(hd),
+                _p(hr), 0 if hr is None else len(hr), _p(hm), _p(ht), float(self.dt), self._stream()))
+            self.time_step = 0
+            return
         self._chk(self._api["amp_reset_rows"](self._phys._h, C.byref(c), C.byref(b), _p(env_ids.contiguous()), n, _p(ps), _p(nz), _p(cx), _p(cy), _p(cyaw),
                                               _p(qb), _p(quatb), _p(ptime), _p(didx), self._stream()))
         self.time_step = 0
         self._reset_default_env_ids = env_ids
+
+    def _draw_starts(self, env_ids):
+        """_reset_actors' draws for the fused reset (amp_motion_device), made as _reset_actors makes them: Hybrid's Bernoulli from torch's
+        generator, the motions and times from numpy's through the motion library's own sampler; the id lists are kept as _reset_default /
+        _reset_ref_state_init keep them.  -> per listed env: kind (int32, 1 = motion start), motion id (int32), time (float64), on the
+        device; the ids and the times cross in one copy each."""
+        ml, n, dev = self._motion_lib, len(env_ids), self._tdev
+        ref = None
+        if self._state_init == "Hybrid":
+            ref = self._rng.bernoulli(n, self._hybrid_init_prob) == 1.0
+            ref_ids, def_ids = env_ids[ref], env_ids[~ref]
+        else:
+            ref_ids, def_ids = env_ids, env_ids[:0]
+        kind = torch.ones(n, dtype=torch.int32, device=dev) if ref is None else ref.to(torch.int32)
+        mids, times = torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.float64, device=dev)
+        if len(ref_ids) > 0:
+            motion_ids = ml.sample_motions(len(ref_ids))
+            motion_times = ml.sample_time(motion_ids) if self._state_init in ("Random", "Hybrid") else np.zeros(len(ref_ids))
+            m_d = torch.tensor(np.ascontiguousarray(motion_ids), dtype=torch.int32, device=dev)
+            t_d = torch.tensor(np.ascontiguousarray(motion_times), dtype=torch.float64, device=dev)
+            if ref is None:
+                mids, times = m_d, t_d
+            else:
+                mids[ref], times[ref] = m_d, t_d
+            self._reset_ref_env_ids = ref_ids
+            self._reset_ref_motion_ids, self._reset_ref_motion_times = motion_ids, motion_times
+            self._reset_ref_dev = (m_d, t_d)
+        if len(def_ids) > 0:
+            self._reset_default_env_ids = def_ids
+        return kind, mids, times
 
     # ------------------------------------------------------------------ state initialisation (tasks/tocabi_amp_lower.py:149-256)
     def _reset_actors(self, env_ids):
@@ -504,8 +559,12 @@ class TocabiAMPLower(VecTask):
         """build_amp_observations (:310-350) on device tensors; dof_pos / dof_vel either the two halves of dof_state or [M,12]."""
         n = root_states.shape[0]
         assert root_states.is_contiguous() and key_pos.is_contiguous() and out.is_contiguous()
-        assert dof_pos.stride() == dof_vel.stride()
-        self._chk(self._api["amp_disc_observations"](n, _p(root_states), _p(dof_pos), _p(dof_vel), dof_pos.stride(0), dof_pos.stride(1),
+        # (a tensor of ONE row may carry any row stride -- torch ignores the stride of a dimension of size 1, so .contiguous() leaves it, and the
+        #  motion library's tensors of a single query come with 1 there: a reset with exactly one reference start.  No second row is read.)
+        es = dof_pos.stride(1)
+        assert es == dof_vel.stride(1) and (n == 1 or dof_pos.stride(0) == dof_vel.stride(0))
+        row = dof_pos.stride(0) if n > 1 else max(dof_pos.stride(0), 12 * es - (es - 1))
+        self._chk(self._api["amp_disc_observations"](n, _p(root_states), _p(dof_pos), _p(dof_vel), row, es,
                                                      int(self._local_root_obs), _p(key_pos), key_pos.shape[1], _p(out), self._stream()))
         return out
 
@@ -543,15 +602,40 @@ class TocabiAMPLower(VecTask):
         if self._motion_lib is None:
             raise RuntimeError("fetch_amp_obs_demo needs the motion library: set cfg.env.motion_file")
         ml, steps = self._motion_lib, self._num_amp_obs_steps
+        if self._motion_device and self._device_draws:
+            # motions and phases from a generator on the device (inverse CDF over the cumulative weights; float64 phase * length): no host copy
+            tab = self._motion_tab
+            if self._demo_gen is None:
+                self._demo_gen = torch.Generator(device=self._tdev)
+                self._demo_gen.manual_seed(int(self.cfg.get("seed", 42)) + 1)
+            u = torch.rand(2, num_samples, dtype=torch.float64, device=self._tdev, generator=self._demo_gen)
+            m_d = torch.searchsorted(tab.cum_weight, u[0], right=True).clamp_(max=tab.num_motions() - 1)
+            t_d = u[1] * tab.length[m_d]
+            return self._fetch_demo_device(num_samples, m_d.to(torch.int32), t_d)
         motion_ids = ml.sample_motions(num_samples)
         if self._amp_obs_demo_buf is None:
             self._amp_obs_demo_buf = torch.zeros(num_samples, steps, NUM_AMP_OBS_PER_STEP, dtype=torch.float, device=self._tdev)
         else:
             assert self._amp_obs_demo_buf.shape[0] == num_samples
         times0 = ml.sample_time(motion_ids)
+        if self._motion_device:
+            return self._fetch_demo_device(num_samples, torch.tensor(np.ascontiguousarray(motion_ids), dtype=torch.int32, device=self._tdev),
+                                           torch.tensor(np.ascontiguousarray(times0), dtype=torch.float64, device=self._tdev))
         mids = np.tile(np.expand_dims(motion_ids, axis=-1), [1, steps]).flatten()
         times = (np.expand_dims(times0, axis=-1) + (-self.dt * np.arange(0, steps))).flatten()
         self._amp_obs_demo_buf[:] = self._motion_amp_obs(mids, times).view(self._amp_obs_demo_buf.shape)
+        return self._amp_obs_demo_buf.view(-1, self.num_amp_obs)
+
+    def _fetch_demo_device(self, num_samples, motion_ids, times0):
+        """fetch_amp_obs_demo's gather, blends and observations as ONE launch into _amp_obs_demo_buf (dw_amp_motion_obs; the ids come from
+        the library's own samplers, so they are not read back to be checked)."""
+        steps = self._num_amp_obs_steps
+        if self._amp_obs_demo_buf is None:
+            self._amp_obs_demo_buf = torch.zeros(num_samples, steps, NUM_AMP_OBS_PER_STEP, dtype=torch.float, device=self._tdev)
+        else:
+            assert self._amp_obs_demo_buf.shape[0] == num_samples
+        self._chk(self._api["amp_motion_obs"](C.byref(self._motion_tab.struct()), num_samples, steps, _p(motion_ids), _p(times0), float(self.dt), 0,
+                                              int(self._local_root_obs), _p(self._amp_obs_demo_buf), 0, self._stream()))
         return self._amp_obs_demo_buf.view(-1, self.num_amp_obs)
 
     # ------------------------------------------------------------------ observations (:540-610)
@@ -800,7 +884,7 @@ class TocabiAMPLower(VecTask):
     def reset_done(self):
         """VecTask.reset_done (tasks/base/vec_task.py:376-391).  With the fused reset and device draws: ONE launch over all envs
         (dw_amp_reset_done acts on the envs whose reset_buf is set), queued before the host asks which envs those were."""
-        if not (self._device_draws and self._state_init == "Default"):
+        if not (self._device_draws and (self._state_init == "Default" or self._motion_device)):
             return super().reset_done()
         # The ids go back to the host as a tensor of their own length, so the host has to learn the count.  dw_amp_reset_ids (ONE launch, queued
         # BEFORE the reset, which clears the flags) compacts the ids on the device and stores their number straight into pinned host memory; the
@@ -819,13 +903,27 @@ class TocabiAMPLower(VecTask):
                                              self._cnt_pin.data_ptr(), self._stream()))
         self._cnt_evt.record(torch.cuda.current_stream(self._tdev))
         c, b = self._fused_tables()
-        self._chk(self._api["amp_reset_done"](self._phys._h, C.byref(c), C.byref(b), None, self._stream()))
+        motion = self._state_init != "Default"
+        if motion:
+            # the start of every resetting env is drawn in the kernel too (three more words of the env's reset key); this form has no torch
+            # twin: the history of the envs that reset is initialised and of no others (the stale-list quirk of _init_amp_obs is not carried)
+            if self._drawn_start is None:
+                self._drawn_start = (torch.full((self.num_envs,), -1, dtype=torch.int32, device=self._tdev),
+                                     torch.full((self.num_envs,), -1, dtype=torch.int32, device=self._tdev),
+                                     torch.zeros(self.num_envs, dtype=torch.float64, device=self._tdev))
+            dk, dm, dt_ = self._drawn_start
+            self._chk(self._api["amp_reset_done_motion"](self._phys._h, C.byref(c), C.byref(b), C.byref(self._motion_tab.struct()),
+                                                         STATE_INITS.index(self._state_init), self._hybrid_init_prob, float(self.dt), _p(dk), _p(dm), _p(dt_),
+                                                         self._stream()))
+        else:
+            self._chk(self._api["amp_reset_done"](self._phys._h, C.byref(c), C.byref(b), None, self._stream()))
         self.obs_dict["obs"] = self._obs_out
         self._cnt_evt.synchronize()
         ids = ids_all[:int(self._cnt_pin[0])]
         if len(ids) > 0:
             self.time_step = 0          # (as reset_idx: only when some env was reset)
-            self._reset_default_env_ids = ids
+            if not motion:
+                self._reset_default_env_ids = ids
         return self.obs_dict, ids
 
     def _step_body(self, actions):
