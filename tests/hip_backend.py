@@ -72,6 +72,8 @@ class HipSim:
         db = abi.DwBuffers()
         for name in abi.BUFFER_NAMES:
             setattr(db, name, self._dev[name].data_ptr())
+        self._up()          # dw_bind reads height_samples (the coarse bound table of the field is built there): the samples first
+        torch.cuda.synchronize()
         _lib.check(self.api, self.api["bind"](self.h, C.byref(db)))
 
     def _up(self):

@@ -978,11 +978,11 @@ def test_whole_step_vs_oracle_at_the_build_boundaries(task_const, k, extra):
 _THRESHOLD_TERMS, _THRESHOLD_STEPS = [8, 11, 12], np.array([0.2, 0.2, 0.05])
 
 
-def _dr_rollout_vs_oracle(task_const, N, wave_build, total_reward_p99):
+def _dr_rollout_vs_oracle(task_const, N, wave_build, total_reward_p99, terrain=None):
     from hip_backend import make_env
     # isolated reset flips per step, and envs that may leave the comparison in all: 4 and 16 at 2048 envs, in proportion to N
     max_flips, max_left = 4 * N // 2048, 16 * N // 2048
-    env = make_env(N, debug_wave_build=wave_build, friction_dr=True, seed=21)
+    env = make_env(N, debug_wave_build=wave_build, friction_dr=True, seed=21, terrain=terrain)
     rng = np.random.default_rng(3)
     env._buf["friction_scale"].copy_(torch.from_numpy(rng.uniform(0.7, 1.3, size=N).astype(np.float32)).cuda())
     env._buf["dof_damping"].copy_(torch.from_numpy((0.1 + rng.uniform(0, 2.9, size=(N, 33))).astype(np.float32)).cuda())
@@ -1038,10 +1038,11 @@ def _dr_rollout_vs_oracle(task_const, N, wave_build, total_reward_p99):
 _STEP_BUFFERS = ("env_state", "root_states", "dof_state", "obs_buf", "rew_buf", "reset_buf", "obs_history", "dof_damping")
 
 
-def _dr_rollout_buffers(N, wave_build):
-    """10 steps with mass / damping / armature / friction DR and random actions; the buffers afterwards."""
+def _dr_rollout_buffers(N, wave_build, terrain=None):
+    """10 steps with mass / damping / armature / friction DR and random actions; the buffers afterwards (terrain: the mapping
+    make_env takes, None = the ground plane)."""
     from hip_backend import make_env
-    env = make_env(N, debug_wave_build=wave_build, friction_dr=True, seed=21)
+    env = make_env(N, debug_wave_build=wave_build, friction_dr=True, seed=21, terrain=terrain)
     g = torch.Generator(device="cuda").manual_seed(8)
     for _ in range(10):
         env.step(torch.rand(N, 13, generator=g, device="cuda") * 2 - 1)
