@@ -7,9 +7,8 @@ grad_norm 0.5 on the actor, e_clip 0.2, clip_value False, entropy_coef 0, bounds
   * the default (`mfma=True`), FOUR launches on the matrix cores: dwp_mlp | dwp_wgrad | dwp_grad_stats | dwp_adam_finish.  Sharded over
     several ranks (`world > 1`): dwp_mlp | dwp_wgrad | dwp_grad_bucket | ONE all-reduce of the 1.61 MB gradient bucket | dwp_grad_stats |
     dwp_adam_finish -- the still-scaled gradients are averaged before unscale / clip / step, as the reference's Horovod
-    `optimizer.synchronize()` does (a2c_continuous_seperate.py:171-180).  `merged_tail=True` runs the last two launches as one
-    (dwp_stats_adam_finish: the same time, off by default); `policy_copy_per_update=False` leaves the rollout policy's fp32 copy of the
-    weights to one `sync_policy_copy()` per epoch (what examples/ppo_consumer.py does).
+    `optimizer.synchronize()` does (a2c_continuous_seperate.py:171-180).  `policy_copy_per_update=False` leaves the rollout policy's
+    fp32 copy of the weights to one `sync_policy_copy()` per epoch (what examples/ppo_consumer.py does).
   * the library-GEMM form (`mfma=False`), 17 launches:
     stage (1 launch) | 3 batched GEMMs + 2 bias-relu | loss (1) | 5 batched GEMMs + 2 relu-backward | grad stats, Adam, finish (3)
 
@@ -178,18 +177,14 @@ class FusedPpoUpdate:
     be captured in a hipGraph once and replayed)."""
 
     def __init__(self, net, cfg: dict, minibatch: int, num_minibatches: int, device, mfma: bool = True, rowmajor: bool = True, split_tail: bool = False,
-                 merged_tail: bool = False, policy_copy_per_update: bool = True, world: int = 1, group=None, collective: bool = None, fp16_grads: bool = False):
+                 policy_copy_per_update: bool = True, world: int = 1, group=None, collective: bool = None, fp16_grads: bool = False):
         """mfma: forward, loss and input gradients in ONE launch on the matrix cores (dwp_mlp + dwp_wgrad; the minibatch must be a multiple of 32, else the library-GEMM form runs) instead
         of eight library GEMM launches with six kernels between them.  rowmajor (mfma only): dwp_mlp also writes its activations and their
         gradients as plain [2, B, 256] / [B, 512] matrices (x16, h1, h2, dh2, dh1: what the tests read); a trainer passes False.
-        merged_tail (mfma only): dwp_grad_stats and dwp_adam_finish as ONE launch whose blocks wait for each other's share of the norm,
-        dwp_stats_adam_finish -- three launches per update (plus dwp_grad_bucket and the all-reduce when sharded).  Measured: exactly as long as the
-        two launches it replaces (profiles/r06_ppo_tail_forms.txt), so it is off by default; the actor's step may differ from theirs in the last place
-        (the norm's partial sums are taken in another order).  barrier_timed_out() reports the one way the merged launch can fail.
         policy_copy_per_update (mfma only): every update's Adam launch also rewrites the fp32 operand-order copy dwp_policy reads (401 408 scattered
         words, 1.1 us of the launch).  False: the updates leave that copy alone and `sync_policy_copy()` -- one launch -- brings it up to date; a
         trainer calls it once after an epoch's updates.  `policy()` refuses to run on a copy it knows to be stale.
-        split_tail (mfma only): the last launch, dwp_adam_finish, as dwp_adam + dwp_finish (five launches: what a test compares the merged one with).
+        split_tail (mfma only): the last launch, dwp_adam_finish, as dwp_adam + dwp_finish (five launches: what a test compares the one launch with).  These are the tail's two forms.
         world, group (mfma only): the ranks that train together (torch.distributed, backend nccl = RCCL) -- every update then averages the
         ranks' gradients with ONE all-reduce of the 1.61 MB bucket between dwp_wgrad and dwp_grad_stats (`update()` =
         `update_head()`, `allreduce()`, `update_tail()`).  collective: run that bucket path although world == 1 (tests: bit-identical to the
@@ -211,7 +206,6 @@ class FusedPpoUpdate:
         self.dev = torch.device(device)
         self.B, self.nmb = int(minibatch), int(num_minibatches)
         self.split_tail = bool(split_tail)
-        self.merged_tail = bool(merged_tail) and not self.split_tail
         self.policy_copy_per_update = bool(policy_copy_per_update)
         self._policy_copy_stale = False
         self.world, self.group = int(world), group
@@ -412,37 +406,22 @@ class FusedPpoUpdate:
             dist.all_reduce(self.bucket, group=self.group)
 
     def update_tail(self):
-        """Second part: statistics, clip, Adam and the scaler on the (averaged) gradient -- dwp_stats_adam_finish, or dwp_grad_stats and dwp_adam_finish."""
+        """Second part: statistics, clip, Adam and the scaler on the (averaged) gradient -- dwp_grad_stats, then dwp_adam_finish (or dwp_adam and dwp_finish)."""
         api, st, B = self.api, self.state.data_ptr(), self.B
         s = torch.cuda.current_stream(self.dev).cuda_stream
         p32f = self.p32f.data_ptr() if self.policy_copy_per_update else None
         self._policy_copy_stale = not self.policy_copy_per_update
-        if self.merged_tail:
-            g, gb, nsl = (self.bucket.data_ptr(), self.bucket.data_ptr() + 4 * NWT, 1) if self.collective else (self.g32.data_ptr(), self.gb.data_ptr(), K["DWP_WGRAD_SLABS"])
-            self._chk(api["stats_adam_finish"](self.p.data_ptr(), self.p16.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), gb, st, self.part.data_ptr(), self.max_norm,
-                                               self.p16t.data_ptr(), g, nsl, p32f, B, self.nmb, 2000, self.pbuf.data_ptr(),
-                                               None if self.collective else self.pbuf.data_ptr(), s))
-            return
-        if self.collective:
-            gb = self.bucket.data_ptr() + 4 * NWT
-            self._chk(api["grad_stats"](None, gb, st, self.part.data_ptr(), None, self.bucket.data_ptr(), 1, s))
-            self._chk(api["adam_finish"](self.p.data_ptr(), self.p16.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), gb, st, self.part.data_ptr(),
-                                         self.max_norm, self.p16t.data_ptr(), self.bucket.data_ptr(), 1, p32f, B, self.nmb, 2000, self.pbuf.data_ptr(), s))
-            return
-        nsl = K["DWP_WGRAD_SLABS"]
-        self._chk(api["grad_stats"](None, self.gb.data_ptr(), st, self.part.data_ptr(), self.pbuf.data_ptr(), self.g32.data_ptr(), nsl, s))
+        # sharded: the averaged bucket [weights | biases] is the gradient; else dwp_wgrad's slabs, and the bias gradients still in pbuf's buckets
+        g, gb, nsl, pbuf_stats = ((self.bucket.data_ptr(), self.bucket.data_ptr() + 4 * NWT, 1, None) if self.collective else
+                                  (self.g32.data_ptr(), self.gb.data_ptr(), K["DWP_WGRAD_SLABS"], self.pbuf.data_ptr()))
+        self._chk(api["grad_stats"](None, gb, st, self.part.data_ptr(), pbuf_stats, g, nsl, s))
         if self.split_tail:
-            self._chk(api["adam"](self.p.data_ptr(), self.p16.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), None, self.gb.data_ptr(), st,
-                                  self.part.data_ptr(), self.max_norm, self.p16t.data_ptr(), self.g32.data_ptr(), nsl, p32f, s))
-            self._chk(api["finish"](st, self.gb.data_ptr(), B, self.nmb, 2000, self.pbuf.data_ptr(), s))
+            self._chk(api["adam"](self.p.data_ptr(), self.p16.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), None, gb, st,
+                                  self.part.data_ptr(), self.max_norm, self.p16t.data_ptr(), g, nsl, p32f, s))
+            self._chk(api["finish"](st, gb, B, self.nmb, 2000, self.pbuf.data_ptr(), s))
             return
-        self._chk(api["adam_finish"](self.p.data_ptr(), self.p16.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.gb.data_ptr(), st, self.part.data_ptr(),
-                                     self.max_norm, self.p16t.data_ptr(), self.g32.data_ptr(), nsl, p32f, B, self.nmb, 2000, self.pbuf.data_ptr(), s))
-
-    def barrier_timed_out(self) -> bool:
-        """True once a block of dwp_stats_adam_finish gave up waiting at its grid barrier (the launch did not have the device to itself for tens of
-        ms): that update was published as skipped (DWP_S_OUT[7] = 2) but some blocks may have stepped -- reload a checkpoint.  Synchronises."""
-        return bool(self.part[642].item() != 0.0)
+        self._chk(api["adam_finish"](self.p.data_ptr(), self.p16.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), gb, st, self.part.data_ptr(),
+                                     self.max_norm, self.p16t.data_ptr(), g, nsl, p32f, B, self.nmb, 2000, self.pbuf.data_ptr(), s))
 
     def update(self):
         """Enqueue one minibatch update on the current stream."""

@@ -1,4 +1,4 @@
-"""include/dyros_ppo.h, ABI version 9: dwp_play and dwp_play_work_floats are declared, mirrored in ppo_update.EXPORTS and exported by the built
+"""include/dyros_ppo.h, ABI version 10: dwp_play (there since 9) and dwp_play_work_floats are declared, mirrored in ppo_update.EXPORTS and exported by the built
 library; the play kernels use no scratch, run their products on v_mfma_f32_16x16x4_f32 only, and no kernel name joins the sets other tests select
 by substring (hipcc with the flags of build.py; no GPU needed)."""
 import ctypes
@@ -19,10 +19,10 @@ TAKEN = ("k_mlp", "k_wgrad", "k_policy", "k_adam", "k_grad_stats", "k_finish", "
 def test_play_is_declared_mirrored_and_exported():
     hdr = open(os.path.join(ROOT, "include", "dyros_ppo.h")).read()
     assert re.search(r"\bint dwp_play\s*\(", hdr) and re.search(r"\bint dwp_play_work_floats\s*\(", hdr)
-    assert ppo_update.K["DWP_ABI_VERSION"] == 9
+    assert ppo_update.K["DWP_ABI_VERSION"] == 10
     assert {"play", "play_work_floats"} <= set(ppo_update.EXPORTS)
     lib = ctypes.CDLL(build.build())
-    assert hasattr(lib, "dwp_play") and hasattr(lib, "dwp_play_work_floats") and lib.dwp_abi_version() == 9
+    assert hasattr(lib, "dwp_play") and hasattr(lib, "dwp_play_work_floats") and lib.dwp_abi_version() == 10
     f = lib.dwp_play_work_floats
     f.restype, f.argtypes = ctypes.c_int, [ctypes.c_int32]
     assert f(1) == 2 * 256 and f(64) == 64 * 2 * 256 and f(65) == 0 and f(16384) == 0
