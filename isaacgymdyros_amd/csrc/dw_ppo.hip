@@ -1439,21 +1439,27 @@ int dwp_rollout_pre(const float *mu, const float *value, const float *noise, con
         return fail("dwp_rollout_pre: bad argument");
     if (((size_t)N * num_obs) % 4) return fail("dwp_rollout_pre: N * num_obs must be a multiple of 4");
     RollPre A{mu, value, noise, obs, dones, logstd, (const long long *)n, mb_obs, mb_act, mb_mu, mb_nlp, mb_val, mb_done, act, N, num_obs, env_major_steps, obs_half, H};
-    hipLaunchKernelGGL(k_roll_pre, dim3((unsigned)(((size_t)N * num_obs / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
+    // one thread serves four observation words, one action word and one 16-byte piece of an fp16 row: the grid covers the largest of the three
+    // counts (the observation copy alone is short of the N * ACT action words once num_obs < 4 * ACT)
+    size_t work = (size_t)N * num_obs / 4;
+    if (work < (size_t)N * ACT) work = (size_t)N * ACT;
+    if (work < (size_t)N * (((size_t)num_obs + 7) / 8)) work = (size_t)N * (((size_t)num_obs + 7) / 8);
+    hipLaunchKernelGGL(k_roll_pre, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
     return done("dwp_rollout_pre");
 }
 
 int dwp_rollout_post(const float *rew, const float *value, const int64_t *time_outs, const float *stacked, int32_t stacked_cols, const int64_t *done_buf, const float *new_obs,
                      const int64_t *n, int32_t N, int32_t num_obs, float reward_scale, float gamma, float *mb_rew, float *terms, int32_t num_terms, float *g_dones,
                      float *g_obs, int32_t H, void *stream) {
-    if (!rew || !value || !done_buf || !new_obs || !n || !mb_rew || !g_dones || !g_obs || N < 1 || H < 1 ||
+    if (!rew || !value || !done_buf || !new_obs || !n || !mb_rew || !g_dones || !g_obs || N < 1 || num_obs < 1 || H < 1 ||
         (terms && (!stacked || num_terms < 1 || num_terms > ROLL_TERMS_MAX || stacked_cols < num_terms)))
         return fail("dwp_rollout_post: bad argument");
     if (((size_t)N * num_obs) % 4) return fail("dwp_rollout_post: N * num_obs must be a multiple of 4");
     RollPost A{rew, value, stacked, new_obs, (const long long *)time_outs, (const long long *)done_buf, (const long long *)n, mb_rew, terms, g_dones, g_obs, N, num_obs,
                num_terms, stacked_cols, reward_scale, gamma, H};
-    // (without the observation copy -- the caller's policy reads the env's own buffer -- the launch covers the envs only)
-    const size_t work = g_obs != new_obs ? (size_t)N * num_obs / 4 : (size_t)N;
+    // (without the observation copy -- the caller's policy reads the env's own buffer -- the launch covers the envs only; with it, the larger
+    //  of the copy's 16-byte pieces and the envs: below four words per row the copy alone is short of the envs)
+    const size_t work = g_obs != new_obs && (size_t)N * num_obs / 4 > (size_t)N ? (size_t)N * num_obs / 4 : (size_t)N;
     hipLaunchKernelGGL(k_roll_post, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
     return done("dwp_rollout_post");
 }
