@@ -259,7 +259,9 @@ typedef struct DwConfig {
 #define DW_ES_PERT_TIMING   339   /* i: */
 #define DW_ES_PERT_START    340   /* i: */
 #define DW_ES_HIST_HEAD     341   /* i: ring position of the OLDEST history slot */
-#define DW_ES_NAN_RESETS    342   /* i: count of resets forced by a non-finite state */
+#define DW_ES_NAN_RESETS    342   /* i: count of resets forced by a non-finite state: dw_step scans the env's 13 root_states words and 66 dof_state
+                                     words after the physics; on a NaN / Inf it rewrites the root to the initial height, zeroes the joints and
+                                     the env's contact_forces row, counts here and resets the env in the same launch; no other env is touched */
 #define DW_ES_EPI_RETURN    343   /* sum of rew_buf over the running episode (logging; a2c_common_dyros.py:661-687 keeps it in torch) */
 #define DW_ES_WARM          344   /* [8][3] contact impulses of the previous substep (warm start) */
 #define DW_ES_LAST_RETURN   368   /* return of the last finished episode */

@@ -240,6 +240,13 @@ DQ_HD void oct_task_post(OSlots &L, const DevModel &M, const TaskParams &C, cons
     DQ_STAMP(B, 42);
     // @phase post_q1
     // ---- Q1: clocks, VecTask counters, non-finite guard ----
+    // The guard (twin: oracle/dw_task.c step_env; tests/nonfinite_cases.py).  Scanned after the physics: the 13 root words of the env by
+    // its first lane, its 66 joint words (q and qd of the 33 joints) by the item lanes that hold them.  An env with a NaN or an Inf in
+    // any of the 79 gets: root = (0, 0, initial_height; identity; zero velocity), q = qd = 0, its contact_forces row and the two sole
+    // forces zeroed, its collision flag cleared, DW_ES_NAN_RESETS + 1 -- so this step's reward and observation are finite -- and is reset
+    // in this launch (Q3 sets `reset`, post_reset rewrites the rows).  Every write is indexed by the bad env (el / ee / i / ND): the
+    // other envs of the wave, and the padding lanes of a partial last wave (copies of env N - 1, nothing of theirs is stored), are
+    // left exactly as an unpoisoned run leaves them.  dw_simulate and the fused TocabiAMPLower step carry no guard.
     if (j == 0) {
         const long long p = q1_progress, rbl = q1_randomize;
         int rb = (int)(rbl > 0x7ffffffe ? 0x7ffffffe : rbl);

@@ -108,8 +108,9 @@ DW_HD void motion_cross(const float *v, const float *m, float *c) {
 DW_HD void terrain_sample(const PhysParams &P, float x, float y, float *h, float *fr) {
     float u = (x + P.t_border) * P.t_inv_h, v = (y + P.t_border) * P.t_inv_h;
     const float umax = (float)(P.t_rows - 1) - 1e-3f, vmax = (float)(P.t_cols - 1) - 1e-3f;
-    u = u < 0.0f ? 0.0f : (u > umax ? umax : u);
-    v = v < 0.0f ? 0.0f : (v > vmax ? vmax : v);
+    // (u > 0 first: a NaN coordinate fails it and lands on cell 0, as motion_frame in dw_amp_motion.h; (int)NaN is undefined)
+    u = u > 0.0f ? (u > umax ? umax : u) : 0.0f;
+    v = v > 0.0f ? (v > vmax ? vmax : v) : 0.0f;
     const int i = (int)u, j = (int)v;
     const float a = u - (float)i, b = v - (float)j;
     const int16_t *p = P.hs + (size_t)i * P.t_cols + j;
@@ -166,8 +167,8 @@ DW_HD float terrain_bound(const PhysParams &P, float x, float y) {
     if (!P.hmax) return 3.0e38f;
     float u = (x + P.t_border) * P.t_inv_h, v = (y + P.t_border) * P.t_inv_h;
     const float umax = (float)(P.t_rows - 1) - 1e-3f, vmax = (float)(P.t_cols - 1) - 1e-3f;
-    u = u < 0.0f ? 0.0f : (u > umax ? umax : u);
-    v = v < 0.0f ? 0.0f : (v > vmax ? vmax : v);
+    u = u > 0.0f ? (u > umax ? umax : u) : 0.0f;          // (NaN -> cell 0, as terrain_sample)
+    v = v > 0.0f ? (v > vmax ? vmax : v) : 0.0f;
     const int ci = (int)u / P.hm_cell, cj = (int)v / P.hm_cell;
     return P.t_vs * (float)P.hmax[(size_t)ci * P.hm_cols + cj];
 }

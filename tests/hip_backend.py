@@ -103,6 +103,23 @@ class HipSim:
         _lib.check(self.api, self.api["step"](self.h, a.data_ptr(), 0 if nz is None else nz.data_ptr(), step_index, torch.cuda.current_stream().cuda_stream))
         self._down()
 
+    def reset_idx(self, env_ids, noise=None, step_index=0):
+        from isaacgymdyros_amd import _lib
+        self._up()
+        ids = torch.from_numpy(np.ascontiguousarray(env_ids, dtype=np.int32)).cuda()
+        nz = None if noise is None else torch.from_numpy(np.ascontiguousarray(noise, dtype=np.float32)).cuda()
+        _lib.check(self.api, self.api["reset_idx"](self.h, ids.data_ptr(), ids.numel(), 0 if nz is None else nz.data_ptr(), step_index,
+                                                   torch.cuda.current_stream().cuda_stream))
+        self._down()
+
+    def terrain_log(self):
+        """[N, 15 + terrain types] (dw_terrain_log), after a step."""
+        from isaacgymdyros_amd import _lib
+        out = torch.zeros((self.N, abi.K["DW_NUM_REW"] + int(self.cfg.terrain_num_types)), dtype=torch.float32, device="cuda:0")
+        _lib.check(self.api, self.api["terrain_log"](self.h, out.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+        return out.cpu().numpy()
+
     def close(self):
         if self.h is not None:
             torch.cuda.synchronize()
