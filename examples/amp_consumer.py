@@ -26,6 +26,10 @@ epoch numbering continues and --epochs more epochs run.
 
 --policy_backend hip runs the actor-critic on isaacgymdyros_amd/amp_policy.py's AmpActorCritic instead (the rollout forward, the bootstrap
 values, GAE, the value normaliser and the minibatch updates on the dwa_ kernels); the default, torch, is the inline loop below.
+
+--episode-stats switches on the env's on-GPU episode statistics (cfg sim.mi355.amp_episode_stats, isaacgymdyros_amd/amp_episode_stats.py) for
+either policy backend: one more line per epoch -- the termination causes, the three most frequent contact bodies, the mean episode length
+and return over that epoch's rollout -- and the window restarted per epoch.
 """
 from __future__ import annotations
 
@@ -77,7 +81,7 @@ class ActorCritic(nn.Module):
         return v * torch.sqrt(r.running_var.float() + r.epsilon) + r.running_mean.float()
 
 
-def make_env(n, device, motion_file, synthetic, motion_device=False):
+def make_env(n, device, motion_file, synthetic, motion_device=False, episode_stats=False):
     from isaacgymdyros_amd.tocabi_amp_lower import TocabiAMPLower, default_amp_cfg
     cfg = default_amp_cfg(n, device)
     if synthetic:
@@ -89,7 +93,18 @@ def make_env(n, device, motion_file, synthetic, motion_device=False):
     cfg["env"]["motion_file"] = motion_file
     if motion_device:          # the motion library as a table on the device: fetch_amp_obs_demo is one launch (sim.mi355.amp_motion_device)
         cfg["sim"].setdefault("mi355", {})["amp_motion_device"] = True
+    if episode_stats:
+        cfg["sim"].setdefault("mi355", {})["amp_episode_stats"] = True
     return TocabiAMPLower(cfg, device, 0, True)
+
+
+def episode_line(env, epoch):
+    """--episode-stats: the epoch's window as one line; the next epoch starts a new one."""
+    if env.episode_stats is None:
+        return
+    from isaacgymdyros_amd.amp_episode_stats import format_line
+    print("epoch %d: %s" % (epoch, format_line(env.episode_stats.summary())), flush=True)
+    env.episode_stats.reset_totals()
 
 
 class Checkpoints:
@@ -139,7 +154,7 @@ def train(args):
     tc = AD.load_train_yaml(args.train_yaml) if args.train_yaml else AD.TRAIN_CFG
     c, netc = tc["config"], tc["network"]
     dev = torch.device(args.device)
-    env = make_env(args.num_envs, args.device, args.motion_file, args.synthetic, args.motion_device)
+    env = make_env(args.num_envs, args.device, args.motion_file, args.synthetic, args.motion_device, getattr(args, "episode_stats", False))
     N, H, A = env.num_envs, int(c["horizon_length"]), env.num_actions
     lr0, lr_min, max_epochs = float(c["learning_rate"]), 1e-6, int(args.max_epochs or c["max_epochs"])
     if args.policy_backend == "hip":
@@ -223,6 +238,7 @@ def train(args):
         print("epoch %d  step fps %.0f  total fps %.0f  disc_r %.4f  a_loss %.4f  c_loss %.4f  b_loss %.4f  %s"
               % (epoch, N * H / max(step_time, 1e-9), N * H / total, float(disc_r.mean()), al, cl, bl,
                  "  ".join("%s %.4f" % (k.replace("disc_", ""), v) for k, v in info.items())), flush=True)
+        episode_line(env, epoch)
         vals = [al, cl, bl, float(disc_r.mean()), float(combined.mean())] + list(info.values())
         if not all(math.isfinite(x) for x in vals):
             raise SystemExit("non-finite loss or reward at epoch %d" % epoch)
@@ -285,6 +301,7 @@ def train_hip(args, tc, dev, env, N, H, A, lr0, lr_min, max_epochs):
         print("epoch %d  step fps %.0f  total fps %.0f  disc_r %.4f  a_loss %.4f  c_loss %.4f  b_loss %.4f  %s"
               % (epoch, N * H / max(step_time, 1e-9), N * H / total, float(disc_r.mean()), al, cl, bl,
                  "  ".join("%s %.4f" % (k.replace("disc_", ""), v) for k, v in info.items())), flush=True)
+        episode_line(env, epoch)
         vals = [al, cl, bl, float(disc_r.mean()), float(combined.mean())] + list(info.values())
         if not all(math.isfinite(x) for x in vals):
             raise SystemExit("non-finite loss or reward at epoch %d" % epoch)
@@ -308,6 +325,8 @@ def main():
     ap.add_argument("--output_dir", default=None, help="write checkpoints under <output_dir>/TocabiAMPLower/nn (default: none are written)")
     ap.add_argument("--save_frequency", type=int, default=None, help="a checkpoint every this many epochs (default: the yaml's, 100)")
     ap.add_argument("--checkpoint", default=None, help="resume from this checkpoint")
+    ap.add_argument("--episode-stats", dest="episode_stats", action="store_true",
+                    help="sim.mi355.amp_episode_stats: one more line per epoch with the termination causes, contact bodies, episode length and return")
     train(ap.parse_args())
 
 

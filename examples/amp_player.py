@@ -10,6 +10,10 @@ task's +-1 action space) unless --stochastic.  On --policy_backend hip that is d
 
 rl_games' player defaults are not part of the reference's checkout; the defaults here: --games 100, --max_steps 10000 (more than the 8000-step
 episode, so every game can end on its own).
+
+--report switches on the env's on-GPU episode statistics (cfg sim.mi355.amp_episode_stats, isaacgymdyros_amd/amp_episode_stats.py) and prints
+their table after playing: termination causes and their combinations, contact bodies, episode lengths, reward terms, command tracking and
+sole loads.
 """
 from __future__ import annotations
 
@@ -30,7 +34,7 @@ from amp_consumer import make_env                     # noqa: E402
 
 def run(args):
     dev = torch.device(args.device)
-    env = make_env(args.num_envs, args.device, args.motion_file, args.synthetic)
+    env = make_env(args.num_envs, args.device, args.motion_file, args.synthetic, episode_stats=args.report)
     if args.export_dir:
         CK.export_txt(args.checkpoint, args.export_dir)
     pol, disc = CK.load_policy(args.checkpoint, dev, backend=args.policy_backend, with_disc=True)
@@ -72,6 +76,9 @@ def run(args):
         raise SystemExit("no game ended within --max_steps %d" % args.max_steps)
     av_r, av_s = sum_rewards / games_played, sum_steps / games_played
     print("av reward:", av_r, "av steps:", av_s, flush=True)
+    if args.report:
+        from isaacgymdyros_amd.amp_episode_stats import format_table
+        print(format_table(env.episode_stats.summary()), flush=True)
     if not (math.isfinite(av_r) and math.isfinite(av_s)):
         raise SystemExit("non-finite average")
 
@@ -89,6 +96,7 @@ def main():
     ap.add_argument("--print_disc_prediction", action="store_true", help="env 0's discriminator logit and reward every step")
     ap.add_argument("--export_dir", default=None, help="write the network tensors and the observation normaliser as text files here")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--report", action="store_true", help="sim.mi355.amp_episode_stats: print the episode statistics' table after playing")
     run(ap.parse_args())
 
 

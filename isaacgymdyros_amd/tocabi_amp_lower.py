@@ -43,6 +43,10 @@ against the reference's on synthetic tables (tests/test_amp_motion.py).  The key
 env's observation reads are recomputed from the state just set (dw_body_positions); Isaac Gym's deferred setters would still
 show the pre-reset rows there -- irrelevant for the history, which _init_amp_obs overwrites.
 
+Why episodes end: cfg sim.mi355.amp_episode_stats (default off) adds one launch after every step, whatever its form, that publishes each
+env's termination causes (extras["termination_cause"], a bit mask) and folds episode statistics into a window on the device
+(isaacgymdyros_amd/amp_episode_stats.py).  `episode_stats` in this class' cfg is NOT that: it is the physics host's key.
+
 Not built: `stateInit: Custom` (the task's triangle-mesh terrain origins; the terrain of this task is not wired).
 
 Where this class departs from the task yaml, all of it on purpose: the spawn height is 0.93 m, not the reference's 0.89 (which
@@ -165,6 +169,12 @@ class TocabiAMPLower(VecTask):
         self.perturb = e["perturbation"]
         self.c_x, self.c_y, self.c_yaw = e["command"]["x"], e["command"]["y"], e["command"]["yaw"]
         self.num_obs_his, self.num_obs_skip = e["NumHis"], e["NumSkip"]
+        # cfg sim.mi355.amp_episode_stats: termination causes and episode statistics on the device, one launch after every step
+        # (isaacgymdyros_amd/amp_episode_stats.py); off: None, and step() makes no extra launch.  The key is this
+        # class' own: `episode_stats` is DyrosDynamicWalk's and would make the physics host below build the walk's statistics
+        self._amp_stats_on = cfg["sim"].get("mi355", {}).get("amp_episode_stats", False)
+        if not isinstance(self._amp_stats_on, bool):
+            raise ValueError("sim.mi355.amp_episode_stats must be True or False")
         e["numObservations"] = (NUM_OBS + NUM_ACTIONS) * self.num_obs_his - NUM_ACTIONS            # :83
         e["numActions"] = NUM_ACTIONS
         super().__init__(config=cfg, sim_device=sim_device, graphics_device_id=graphics_device_id, headless=headless)
@@ -175,7 +185,7 @@ class TocabiAMPLower(VecTask):
         pc["sim"].update({k: copy.deepcopy(v) for k, v in cfg["sim"].items() if k != "mi355"})
         # (physx.num_position_iterations + num_velocity_iterations = the contact solver's iteration count, as the task yaml gives them:
         #  4 + 0 for this task, cfg/task/TocabiAMPLower.yaml)
-        pc["sim"]["mi355"].update(cfg["sim"].get("mi355", {}))
+        pc["sim"]["mi355"].update({k: v for k, v in cfg["sim"].get("mi355", {}).items() if k != "amp_episode_stats"})
         pc["env"]["perturbation"] = False
         # spawn height: the reference's 0.89 (:394) puts the soles 2.2 cm INTO the plane in the initial pose; PhysX resolves that
         # positionally, this simulator's contact model through a velocity bias (erp), which launches the robot at 2 m/s.  Default
@@ -339,6 +349,11 @@ class TocabiAMPLower(VecTask):
             mid, sc = 0.5 * (hi + lo), 1.0 * (hi - lo)                                         # :485-503
             self._pd_action_offset = torch.tensor(0.5 * ((mid + sc) + (mid - sc)), **f)
             self._pd_action_scale = torch.tensor(0.5 * ((mid + sc) - (mid - sc)), **f)
+        self.episode_stats = None
+        if self._amp_stats_on:
+            from .amp_episode_stats import AmpEpisodeStats
+            self.episode_stats = AmpEpisodeStats(self)
+            self.extras["termination_cause"] = self.episode_stats.cause
 
     # ------------------------------------------------------------------ helpers
     def _rand(self, *shape):
@@ -927,8 +942,12 @@ class TocabiAMPLower(VecTask):
         return self.obs_dict, ids
 
     def _step_body(self, actions):
-        if self._fused:
-            return self._step_fused(actions)
+        out = self._step_fused(actions) if self._fused else self._step_torch(actions)
+        if self.episode_stats is not None:
+            self.episode_stats.record()          # (fills extras["termination_cause"] in place; every step form ends here)
+        return out
+
+    def _step_torch(self, actions):
         action_tensor = torch.clamp(actions, -self.clip_actions, self.clip_actions)
         self.pre_physics_step(action_tensor)
         self.post_physics_step()
