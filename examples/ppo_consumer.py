@@ -229,9 +229,12 @@ GRAPH_COLLECTIVE = os.environ.get("DW_PPO_GRAPH_COLLECTIVE", "1") == "1"
 POLICY_COPY_PER_UPDATE = os.environ.get("DW_PPO_POLICY_COPY_PER_UPDATE", "0") == "1"
 
 
+TRACE_DRAIN = 8          # held slots of the run trace written per epoch (train(trace_falls=...))
+
+
 def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cfg=None, max_epochs=None, env=None,
           rank=0, world=1, seed=42, graph_rollout=False, graph_update=False, fused_update=False, fused_collective=None, global_gate=False,
-          checkpoint=None, output_dir=None, save_frequency=0, experiment="DyrosDynamicWalk", episode_stats=False):
+          checkpoint=None, output_dir=None, save_frequency=0, experiment="DyrosDynamicWalk", episode_stats=False, trace_falls=None):
     """`epochs` PPO epochs of the DYROS configuration on `num_envs` envs of this rank.  Returns one stats dict per epoch.
     graph_rollout: one rollout step (policy inference, sampling, env step, bookkeeping) is captured once in a hipGraph and
     replayed `horizon` times per epoch -- possible because dw_step_dev keeps the step counter in device memory, so a replayed
@@ -256,7 +259,11 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
     episode_stats: the env's on-GPU episode statistics (cfg sim.mi355.episode_stats, isaacgymdyros_amd/episode_stats.py; their launch sits inside
     the captured rollout step like the rest of env.step): every epoch is one window, its summary goes into the epoch's stats dict as
     "episode_stats" and one more log line gives the termination causes, the three most frequent contact bodies, the mean length and the
-    push falls.  Off: neither the dicts nor the log change."""
+    push falls.  Off: neither the dicts nor the log change.
+    trace_falls: a directory.  The env's on-GPU run trace (cfg sim.mi355.run_trace, isaacgymdyros_amd/run_trace.py; its launch sits inside the
+    captured rollout step too) keeps the last 512 steps of envs 0 .. 63 and freezes a slot at a fall; after every epoch, outside the graphs and
+    with one host sync, at most TRACE_DRAIN held slots are written to <dir>/epoch<e>_fall_env<id>.npz (rank r > 0: ..._rank<r>.npz) and armed
+    again.  The epoch's stats dict gets "trace_falls", the files written."""
     from isaacgymdyros_amd.config import default_cfg
     from isaacgymdyros_amd.dyros_dynamic_walk import DyrosDynamicWalk
     cfg = cfg or TRAIN_CFG
@@ -269,6 +276,8 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
         ecfg["seed"] = seed + rank
         if episode_stats:
             ecfg["sim"]["mi355"]["episode_stats"] = True
+        if trace_falls:
+            ecfg["sim"]["mi355"]["run_trace"] = {"env_ids": min(64, num_envs), "depth": 512, "hold": "fall"}
         if graph_rollout:
             ecfg["sim"]["mi355"]["device_step_counter"] = True
             ecfg["sim"]["mi355"]["alias_obs"] = True          # (the loop copies what it keeps)
@@ -277,6 +286,9 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
     epstats = getattr(env, "episode_stats", None) if episode_stats else None
     if episode_stats and epstats is None:
         raise ValueError("episode_stats needs an env built with cfg sim.mi355.episode_stats = True")
+    trace = getattr(env, "run_trace", None) if trace_falls else None
+    if trace_falls and trace is None:
+        raise ValueError("trace_falls needs an env built with cfg sim.mi355.run_trace")
     torch.manual_seed(seed)                          # same initial weights on every rank
     net = DyrosActorCritic(env.num_obs, env.num_acts, cfg["network"]).to(device)
     torch.manual_seed(seed + 7919 * rank)            # ... but its own exploration noise (Normal.sample draws from the global generator)
@@ -605,6 +617,14 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
         s["frame"] = frame
         if epstats is not None:
             s["episode_stats"] = epstats.summary()
+        if trace is not None:
+            os.makedirs(trace_falls, exist_ok=True)
+            from isaacgymdyros_amd.run_trace import write_npz
+            falls = trace.drain(TRACE_DRAIN)          # (the one sync: the held slots are chosen, gathered and armed again on the device)
+            s["trace_falls"] = [os.path.join(trace_falls, "epoch%d_fall_env%d%s.npz" % (ep, f["env_id"], "_rank%d" % rank if rank else ""))
+                                for f in falls]
+            for f, path in zip(falls, s["trace_falls"]):
+                write_npz(path, f)
         stats.append(s)
         if rank == 0:
             log("epoch %(epoch)d: fps step %(step_fps).3g  step+inference %(play_fps).3g  total %(total_fps).3g  mean reward %(mean_reward).3f  "
@@ -633,6 +653,8 @@ def main():
     ap.add_argument("--output-dir", default=None, help="write checkpoints to <dir>/DyrosDynamicWalk/nn/ (rank 0)")
     ap.add_argument("--save-frequency", type=int, default=None, help="epochs between numbered checkpoints (default: the yaml's 100 with --output-dir)")
     ap.add_argument("--episode-stats", action="store_true", help="on-GPU termination causes and episode statistics, one log line per epoch")
+    ap.add_argument("--trace-falls", default=None, metavar="DIR", help="on-GPU run trace of envs 0..63, frozen at falls: up to 8 falls per epoch "
+                    "are written to DIR as .npz (isaacgymdyros_amd/run_trace.py)")
     a = ap.parse_args()
     save_frequency = a.save_frequency if a.save_frequency is not None else (100 if a.output_dir else 0)
     from isaacgymdyros_amd import dist as dwdist
@@ -640,7 +662,7 @@ def main():
     dev = "cuda:%d" % local_rank
     torch.cuda.set_device(local_rank)
     train(a.num_envs, a.epochs, a.horizon, device=dev, rank=rank, world=world, graph_rollout=a.fused, fused_update=a.fused,
-          checkpoint=a.checkpoint, output_dir=a.output_dir, save_frequency=save_frequency, episode_stats=a.episode_stats)
+          checkpoint=a.checkpoint, output_dir=a.output_dir, save_frequency=save_frequency, episode_stats=a.episode_stats, trace_falls=a.trace_falls)
     if world > 1:
         torch.distributed.destroy_process_group()
 

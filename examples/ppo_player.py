@@ -10,6 +10,11 @@ The action is WalkPolicy.play (isaacgymdyros_amd/walk_policy.py): the actor in e
 identity on this task's +-1 action space (tasks/base/vec_task.py:95) -- or, with --stochastic, clamp(mu + exp(sigma) noise, -1, 1).  On
 --policy-backend hip that is dwp_play.  An episode is 32 s at 4 ms per policy step (8000 steps); --max-steps defaults to 10000, so every game can
 end on its own.
+
+--trace-dir DIR turns the on-GPU run trace on (isaacgymdyros_amd/run_trace.py): the last --trace-depth steps of envs
+0 .. --trace-envs - 1.  With --trace-hold fall (the default) or reset a slot freezes at the step that ends its episode; after each round of games
+the held slots are written to DIR/fall_env<id>_<n>.npz and armed again, and the count is printed at the end.  With never the rings are written
+once at the end, as DIR/ring_env<id>.npz.
 """
 from __future__ import annotations
 
@@ -24,6 +29,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from isaacgymdyros_amd import ppo_checkpoint as PK          # noqa: E402
+
+
+def drain_held(trace, directory: str, n: int) -> int:
+    """Writes every held slot's ring to directory/fall_env<id>_<n>.npz, arms those slots again; returns the new file count."""
+    from isaacgymdyros_amd.run_trace import write_npz
+    for f in trace.drain():
+        write_npz(os.path.join(directory, "fall_env%d_%d.npz" % (f["env_id"], n)), f)
+        n += 1
+    return n
 
 
 def run(args):
@@ -42,7 +56,11 @@ def run(args):
         cfg["env"]["episodeLength"] = float(args.episode_length)
     if args.report:
         cfg["sim"]["mi355"]["episode_stats"] = True
+    if args.trace_dir:
+        cfg["sim"]["mi355"]["run_trace"] = {"env_ids": min(args.trace_envs, args.num_envs), "depth": args.trace_depth, "hold": args.trace_hold}
+        os.makedirs(args.trace_dir, exist_ok=True)
     env = DyrosDynamicWalk(cfg, args.device, 0, True)
+    traces_written = 0
     ck = PK.load(args.checkpoint)
     n_obs, n_act = int(ck["model"][PK.PREFIX + "actor_mlp.0.weight"].shape[1]), int(ck["model"][PK.PREFIX + "mu.weight"].shape[0])
     if (n_obs, n_act) != (env.num_obs, env.num_acts):
@@ -71,11 +89,19 @@ def run(args):
             sum_rewards += cur_r
             sum_steps += cur_s
             print("reward:", cur_r / k, "steps:", cur_s / k, flush=True)
+            if env.run_trace is not None and args.trace_hold != "never":
+                traces_written = drain_held(env.run_trace, args.trace_dir, traces_written)
             if games_played >= args.games:
                 break
     if args.report:
         from isaacgymdyros_amd.episode_stats import format_table
         print(format_table(env.episode_stats.summary()), flush=True)
+    if env.run_trace is not None:
+        if args.trace_hold == "never":
+            for e in env.run_trace.env_ids:
+                env.run_trace.save_npz(os.path.join(args.trace_dir, "ring_env%d.npz" % e), e)
+            traces_written = len(env.run_trace.env_ids)
+        print("run trace: %d files written to %s" % (traces_written, args.trace_dir), flush=True)
     env.close()
     if games_played == 0:
         raise SystemExit("no game ended within --max-steps %d" % args.max_steps)
@@ -97,6 +123,11 @@ def main():
     ap.add_argument("--episode-length", type=float, default=None, help="episode length in seconds (default: the yaml's 32 s)")
     ap.add_argument("--report", action="store_true", help="collect the on-GPU episode statistics and print their table at the end")
     ap.add_argument("--nominal", action="store_true", help="task.randomize False and env.perturbation False (encoder noise stays on)")
+    ap.add_argument("--trace-dir", default=None, help="turn the on-GPU run trace on and write its rings here (fall_env<id>_<n>.npz)")
+    ap.add_argument("--trace-envs", type=int, default=64, help="trace envs 0 .. K-1")
+    ap.add_argument("--trace-depth", type=int, default=512, help="steps kept per traced env")
+    ap.add_argument("--trace-hold", default="fall", choices=["never", "fall", "reset"],
+                    help="freeze a slot at the step that ends its episode: other than by the time limit / at any reset / never")
     ap.add_argument("--device", default="cuda:0")
     run(ap.parse_args())
 

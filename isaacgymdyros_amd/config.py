@@ -104,6 +104,9 @@ def validate_cfg(cfg: dict) -> None:
         raise ValueError("sim.mi355.pipeline must be 0/'auto' or 3/'oct' (1/'fused', 2/'quad' and 4/'lane', the kernels of rounds 1, 2 and 4, are retired)")
     if not isinstance(sim.get("mi355", {}).get("episode_stats", False), bool):
         raise ValueError("sim.mi355.episode_stats must be True or False")
+    if sim.get("mi355", {}).get("run_trace") is not None:
+        from .run_trace import validate as validate_run_trace          # (env ids in range and distinct, depth, hold mode, ring size)
+        validate_run_trace(sim["mi355"]["run_trace"], n)
     iters = int(px.get("num_position_iterations", 4)) + int(px.get("num_velocity_iterations", 1))
     if not 1 <= iters <= 64:
         raise ValueError("physx.num_position_iterations + num_velocity_iterations must be in 1..64")

@@ -103,6 +103,13 @@ class DyrosDynamicWalk(VecTask):
             from .episode_stats import EpisodeStats
             self.episode_stats = EpisodeStats(self)
             self.extras["termination_cause"] = self.episode_stats.cause
+        # cfg sim.mi355.run_trace: a ring of the last steps of chosen envs on the device, one launch after every step, optionally frozen at
+        # a fall (isaacgymdyros_amd/run_trace.py); off: None, and step() makes no extra launch
+        self.run_trace = None
+        spec = self.cfg["sim"].get("mi355", {}).get("run_trace")
+        if spec is not None and spec is not False:          # (as validate_cfg reads it: {} is the default trace)
+            from .run_trace import RunTrace
+            self.run_trace = RunTrace(self, spec)
 
     # ------------------------------------------------------------------ native handle
     def _make_config(self):
@@ -375,6 +382,8 @@ class DyrosDynamicWalk(VecTask):
             self.extras["stacked_rewards"] = log
         if self.episode_stats is not None:
             self.episode_stats.record()          # (fills extras["termination_cause"] in place)
+        if self.run_trace is not None:
+            self.run_trace.record()
         self.obs_dict["obs"] = (self.obs_buf if fresh else self._clip_obs(self.obs_buf)).to(self.rl_device)
         return self.obs_dict, self.rew_buf.to(self.rl_device), self.reset_buf.to(self.rl_device), self.extras
 
@@ -387,6 +396,8 @@ class DyrosDynamicWalk(VecTask):
         _lib.check(self._api, self._api["reset_idx"](self._h, ids.data_ptr(), int(ids.numel()), nz, self._current_step(), stream))
         if self.episode_stats is not None:
             self.episode_stats.restart(ids)          # (the running episodes of these envs are discarded, not counted)
+        if self.run_trace is not None:
+            self.run_trace.arm(ids)
         # (reset_idx does not touch the observations: the reference recomputes them in the next step's post-physics, :655-669)
 
     def _current_step(self) -> int:
@@ -463,6 +474,8 @@ class DyrosDynamicWalk(VecTask):
             self._step_dev.fill_(self._step_count)
         if self.episode_stats is not None:
             self.episode_stats.restart()
+        if self.run_trace is not None:
+            self.run_trace.arm()
 
     def close(self):
         if getattr(self, "_h", None) is not None:
