@@ -30,6 +30,12 @@ values, GAE, the value normaliser and the minibatch updates on the dwa_ kernels)
 --episode-stats switches on the env's on-GPU episode statistics (cfg sim.mi355.amp_episode_stats, isaacgymdyros_amd/amp_episode_stats.py) for
 either policy backend: one more line per epoch -- the termination causes, the three most frequent contact bodies, the mean episode length
 and return over that epoch's rollout -- and the window restarted per epoch.
+
+--game-meter runs the learner's episode-return meter (isaacgymdyros_amd/game_meter.py; the reference's game_rewards and game_lengths over the
+last 100 finished episodes, amp_continuous.py:126-143, common_agent.py:158-168) for either policy backend: one launch after every env.step,
+fed the raw task reward (before reward_scale), and `mean_rewards`, `episode length` and `games` at the end of the epoch line.  The window
+slides over the run.  There are no best files for this learner (common_agent.py has none); last_mean_rewards goes from a checkpoint into
+the files written.
 """
 from __future__ import annotations
 
@@ -107,6 +113,24 @@ def episode_line(env, epoch):
     env.episode_stats.reset_totals()
 
 
+def make_meter(args, N, dev):
+    """--game-meter: the learner's GameMeter, or None."""
+    if not getattr(args, "game_meter", False):
+        return None
+    from isaacgymdyros_amd.game_meter import GameMeter
+    return GameMeter(N, dev, cols=1, games_to_track=100)
+
+
+def meter_text(meter):
+    """The end of the epoch line: empty without --game-meter."""
+    if meter is None:
+        return ""
+    m = meter.summary()          # (one device-to-host copy; the epoch's synchronisation is behind us)
+    if not (math.isfinite(m["mean_reward"]) and math.isfinite(m["mean_length"])):
+        raise SystemExit("non-finite episode return or length in the game meter")
+    return "  mean_rewards %.4f  episode length %.1f  games %d" % (m["mean_reward"], m["mean_length"], m["games"])
+
+
 class Checkpoints:
     """--checkpoint / --output_dir / --save_frequency for one run: resume() before the first epoch, after_epoch() after each, finish() at the end."""
 
@@ -115,6 +139,8 @@ class Checkpoints:
         self.sched = {"lr0": lr0, "lr_min": lr_min, "max_epochs": max_epochs}
         self.dir = os.path.join(args.output_dir, CK.NAME, "nn") if args.output_dir else None
         self.freq = args.save_frequency
+        # --game-meter: a checkpoint's last_mean_rewards goes into the files written (this learner never moves it: common_agent.py)
+        self.last_mean_rewards = CK.LAST_MEAN_REWARDS if getattr(args, "game_meter", False) else None
         if self.freq is None:
             self.freq = CK.SAVE_FREQUENCY
             if args.train_yaml:
@@ -129,6 +155,8 @@ class Checkpoints:
         for k in self.sched:
             if c[k] is not None:
                 self.sched[k] = c[k]
+        if self.last_mean_rewards is not None:
+            self.last_mean_rewards = c["last_mean_rewards"]
         print("resumed %s at epoch %d" % (self.args.checkpoint, c["epoch"]), flush=True)
         return c["epoch"]
 
@@ -137,7 +165,8 @@ class Checkpoints:
         return s["lr_min"] + (s["lr0"] - s["lr_min"]) * max(0, s["max_epochs"] - epoch) / s["max_epochs"]
 
     def _save(self, name, policy, disc, done):
-        path = CK.save(os.path.join(self.dir, name + ".pth"), policy, disc, done, done * self.rows, **self.sched)
+        more = {} if self.last_mean_rewards is None else {"last_mean_rewards": self.last_mean_rewards}
+        path = CK.save(os.path.join(self.dir, name + ".pth"), policy, disc, done, done * self.rows, **self.sched, **more)
         print("saved %s epoch %d lr %.9e" % (path, done, policy.optimizer_state()["lr"]), flush=True)
 
     def after_epoch(self, epoch, policy, disc):
@@ -169,6 +198,7 @@ def train(args):
           "rew": torch.zeros(H, N, 1, device=dev), "done": torch.zeros(H, N, device=dev), "amp": torch.zeros(H, N, env.num_amp_obs, device=dev)}
     ckp, learner = Checkpoints(args, N, H, lr0, lr_min, max_epochs), CK.TorchLearner(model, opt)
     first = ckp.resume(learner, disc)
+    meter = make_meter(args, N, dev)
     env.reset()
     for epoch in range(first, first + args.epochs):
         lr = ckp.lr(epoch)
@@ -187,6 +217,8 @@ def train(args):
                 obs2, rew, done, infos = env.step(torch.clamp(act, -1.0, 1.0))
                 torch.cuda.synchronize(dev)
                 step_time += time.time() - ts
+                if meter is not None:
+                    meter.record(rew, done)
                 mb["rew"][n], mb["done"][n], mb["amp"][n] = rew.view(N, 1) * float(c["reward_scale"]), done.float(), infos["amp_obs"]
                 nv = model.unnorm_value(model(obs2["obs"])[1])
                 mb["next_val"][n] = nv * (1.0 - infos["terminate"].float().view(N, 1))
@@ -235,9 +267,9 @@ def train(args):
         total = time.time() - t0
         info = disc.pop_info()
         al, cl, bl = torch.stack(losses).mean(0).tolist()
-        print("epoch %d  step fps %.0f  total fps %.0f  disc_r %.4f  a_loss %.4f  c_loss %.4f  b_loss %.4f  %s"
+        print("epoch %d  step fps %.0f  total fps %.0f  disc_r %.4f  a_loss %.4f  c_loss %.4f  b_loss %.4f  %s%s"
               % (epoch, N * H / max(step_time, 1e-9), N * H / total, float(disc_r.mean()), al, cl, bl,
-                 "  ".join("%s %.4f" % (k.replace("disc_", ""), v) for k, v in info.items())), flush=True)
+                 "  ".join("%s %.4f" % (k.replace("disc_", ""), v) for k, v in info.items()), meter_text(meter)), flush=True)
         episode_line(env, epoch)
         vals = [al, cl, bl, float(disc_r.mean()), float(combined.mean())] + list(info.values())
         if not all(math.isfinite(x) for x in vals):
@@ -258,6 +290,7 @@ def train_hip(args, tc, dev, env, N, H, A, lr0, lr_min, max_epochs):
           "done": torch.zeros(H, N, device=dev), "amp": torch.zeros(H, N, env.num_amp_obs, device=dev)}
     ckp = Checkpoints(args, N, H, lr0, lr_min, max_epochs)
     first = ckp.resume(pol, disc)
+    meter = make_meter(args, N, dev)
     env.reset()
     for epoch in range(first, first + args.epochs):
         lr = ckp.lr(epoch)
@@ -272,6 +305,8 @@ def train_hip(args, tc, dev, env, N, H, A, lr0, lr_min, max_epochs):
                 obs2, rew, done, infos = env.step(act_c)
                 torch.cuda.synchronize(dev)
                 step_time += time.time() - ts
+                if meter is not None:
+                    meter.record(rew, done)
                 mb["rew"][n], mb["done"][n], mb["amp"][n] = rew.view(N, 1) * float(c["reward_scale"]), done.float(), infos["amp_obs"]
                 mb["next_val"][n] = pol.eval_critic(obs2["obs"].contiguous(), infos["terminate"].float().contiguous())
             combined, disc_r = disc.rewards(mb["amp"], mb["rew"])     # _calc_amp_rewards + _combine_rewards
@@ -298,9 +333,9 @@ def train_hip(args, tc, dev, env, N, H, A, lr0, lr_min, max_epochs):
         total = time.time() - t0
         info, pinfo = disc.pop_info(), pol.pop_info()
         al, cl, bl = pinfo["a_loss"], pinfo["c_loss"], pinfo["b_loss"]
-        print("epoch %d  step fps %.0f  total fps %.0f  disc_r %.4f  a_loss %.4f  c_loss %.4f  b_loss %.4f  %s"
+        print("epoch %d  step fps %.0f  total fps %.0f  disc_r %.4f  a_loss %.4f  c_loss %.4f  b_loss %.4f  %s%s"
               % (epoch, N * H / max(step_time, 1e-9), N * H / total, float(disc_r.mean()), al, cl, bl,
-                 "  ".join("%s %.4f" % (k.replace("disc_", ""), v) for k, v in info.items())), flush=True)
+                 "  ".join("%s %.4f" % (k.replace("disc_", ""), v) for k, v in info.items()), meter_text(meter)), flush=True)
         episode_line(env, epoch)
         vals = [al, cl, bl, float(disc_r.mean()), float(combined.mean())] + list(info.values())
         if not all(math.isfinite(x) for x in vals):
@@ -327,6 +362,8 @@ def main():
     ap.add_argument("--checkpoint", default=None, help="resume from this checkpoint")
     ap.add_argument("--episode-stats", dest="episode_stats", action="store_true",
                     help="sim.mi355.amp_episode_stats: one more line per epoch with the termination causes, contact bodies, episode length and return")
+    ap.add_argument("--game-meter", dest="game_meter", action="store_true",
+                    help="the learner's on-GPU episode-return meter: mean_rewards, episode length and games at the end of the epoch line")
     train(ap.parse_args())
 
 

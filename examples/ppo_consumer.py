@@ -234,7 +234,8 @@ TRACE_DRAIN = 8          # held slots of the run trace written per epoch (train(
 
 def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cfg=None, max_epochs=None, env=None,
           rank=0, world=1, seed=42, graph_rollout=False, graph_update=False, fused_update=False, fused_collective=None, global_gate=False,
-          checkpoint=None, output_dir=None, save_frequency=0, experiment="DyrosDynamicWalk", episode_stats=False, trace_falls=None):
+          checkpoint=None, output_dir=None, save_frequency=0, experiment="DyrosDynamicWalk", episode_stats=False, trace_falls=None,
+          game_meter=False, save_best_after=None, score_to_win=None, games_to_track=100):
     """`epochs` PPO epochs of the DYROS configuration on `num_envs` envs of this rank.  Returns one stats dict per epoch.
     graph_rollout: one rollout step (policy inference, sampling, env step, bookkeeping) is captured once in a hipGraph and
     replayed `horizon` times per epoch -- possible because dw_step_dev keeps the step counter in device memory, so a replayed
@@ -254,8 +255,8 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
     both optimisers (or the fused update's moments, steps and learning rates) and the loss scale; the epochs then continue from the file's epoch + 1
     with the schedule's lr and sigma of those epoch numbers, and `frame` continues.  Every rank restores the same file.
     output_dir (rank 0 writes): <output_dir>/<experiment>/nn/<experiment>_<epoch>.pth every save_frequency epochs (0: never) and
-    <experiment>.pth after the last epoch.  The reference's last_..._ep_<n>_rew_<r> and best-reward names (a2c_common_dyros.py:1036-1075) need
-    per-episode returns, which this loop does not track; the names here are those of examples/amp_consumer.py.
+    <experiment>.pth after the last epoch: the names of examples/amp_consumer.py.  The reference's last_..._ep_<n>_rew_<r> and best-reward
+    names (a2c_common_dyros.py:1036-1075) need per-episode returns: see game_meter below.
     episode_stats: the env's on-GPU episode statistics (cfg sim.mi355.episode_stats, isaacgymdyros_amd/episode_stats.py; their launch sits inside
     the captured rollout step like the rest of env.step): every epoch is one window, its summary goes into the epoch's stats dict as
     "episode_stats" and one more log line gives the termination causes, the three most frequent contact bodies, the mean length and the
@@ -263,7 +264,18 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
     trace_falls: a directory.  The env's on-GPU run trace (cfg sim.mi355.run_trace, isaacgymdyros_amd/run_trace.py; its launch sits inside the
     captured rollout step too) keeps the last 512 steps of envs 0 .. 63 and freezes a slot at a fall; after every epoch, outside the graphs and
     with one host sync, at most TRACE_DRAIN held slots are written to <dir>/epoch<e>_fall_env<id>.npz (rank r > 0: ..._rank<r>.npz) and armed
-    again.  The epoch's stats dict gets "trace_falls", the files written."""
+    again.  The epoch's stats dict gets "trace_falls", the files written.
+    game_meter: the learner's episode-return meter (isaacgymdyros_amd/game_meter.py): the reference's game_rewards and
+    game_lengths over the last games_to_track finished episodes (a2c_common_dyros.py:168-170, 663-684), fed by one launch after every
+    env.step -- inside the captured rollout step in both captured forms -- from the step's reward, reset_buf and stacked reward terms.  It is
+    a sliding window over the run, not cleared per epoch.  Every epoch's stats dict gets "game_meter" (GameMeter.summary(), one device-to-host
+    copy) and one more log line gives the mean return, the mean length and the games.  With output_dir rank 0 then saves by the reference's
+    policy (BestCheckpoints; a2c_common_dyros.py:1039-1075) instead of the names above: last_<experiment>_ep_<n>_rew_<r>.pth every
+    save_frequency epochs while the mean is no new best, <experiment>.pth -- the BEST policy -- when the mean is a new best and the epoch is
+    at least save_best_after (None: the yaml's 200), <experiment>_ep_<n>_rew_<r>.pth and the end of the run past score_to_win (None: the
+    yaml's 20000), and last_<experiment>ep<n>rew<r>.pth, the run's last state, at the end.  The files carry last_mean_rewards, and a
+    checkpoint's value is where the best starts, so a resumed run keeps its best.  Sharded, rank 0's meter decides, as in the reference.
+    Off: nothing changes."""
     from isaacgymdyros_amd.config import default_cfg
     from isaacgymdyros_amd.dyros_dynamic_walk import DyrosDynamicWalk
     cfg = cfg or TRAIN_CFG
@@ -316,6 +328,7 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
     amp = bool(c["mixed_precision"]) and str(device).startswith("cuda")
     scaler = torch.amp.GradScaler("cuda", enabled=amp)
     start, frame = 0, 0
+    best_start = None
     if checkpoint:
         from isaacgymdyros_amd import ppo_checkpoint as PK
         # (before any capture: the weights are written in place -- into the fused update's master buffer, whose copies are refreshed --, and a
@@ -323,15 +336,35 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
         got = (PK.restore(checkpoint, net, fused=fused) if fused is not None else
                PK.restore(checkpoint, net, opt_actor=opt_a, opt_critic=opt_c, scaler=scaler))
         start, frame = got["epoch"], got["frame"]
+        best_start = got["last_mean_rewards"]
         if rank == 0:
             log("restored %s: epoch %d, frame %d" % (checkpoint, start, frame))
 
-    def save(path, epoch):
+    def save(path, epoch, **more):
         from isaacgymdyros_amd import ppo_checkpoint as PK
         kw = dict(fused=fused) if fused is not None else dict(opt_actor=opt_a, opt_critic=opt_c, scaler=scaler)
-        PK.save(path, net, epoch, frame, lr0=float(c["learning_rate"]), lr_min=float(c["learning_rate_min"]), max_epochs=max_epochs, **kw)
+        PK.save(path, net, epoch, frame, lr0=float(c["learning_rate"]), lr_min=float(c["learning_rate_min"]), max_epochs=max_epochs, **kw, **more)
     nn_dir = os.path.join(output_dir, experiment, "nn") if output_dir else None
     names = list(env.extras.get("reward_names", []))
+    meter, best = [None], None
+    if game_meter:
+        from isaacgymdyros_amd import game_meter as GM
+        from isaacgymdyros_amd import ppo_checkpoint as PK
+        if nn_dir and rank == 0:
+            best = GM.BestCheckpoints(experiment, save_frequency, c.get("save_best_after", PK.SAVE_BEST_AFTER) if save_best_after is None else save_best_after,
+                                      c.get("score_to_win", PK.SCORE_TO_WIN) if score_to_win is None else score_to_win,
+                                      GM.LAST_MEAN_REWARDS if best_start is None else best_start)
+
+    def meter_record(r, d, infos):
+        """game_meter: one launch after env.step (a2c_common_dyros.py:663-684).  The meter is built at the first step, which is never a
+        captured one: its columns are the reward and the step's stacked reward terms, where the env gives them."""
+        st = infos.get("stacked_rewards")
+        if st is not None and not (st.dtype == torch.float32 and st.dim() == 2 and st.is_contiguous()):
+            st = None
+        if meter[0] is None:
+            meter[0] = GM.GameMeter(N, device, cols=1 + (min(st.shape[1], GM.COLS_MAX - 1) if st is not None else 0), games_to_track=games_to_track,
+                                    backend="hip" if str(device).startswith("cuda") else "torch")
+        meter[0].record(r, d, st if meter[0].cols > 1 else None)
     obs = env.reset()["obs"].clone()
     dones = torch.zeros(N, device=device)
     if str(device).startswith("cuda"):
@@ -340,7 +373,10 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
         with torch.no_grad():
             mu, logstd, _ = net(obs)
             a = torch.distributions.Normal(mu, torch.exp(logstd)).sample()
-            obs = env.step(torch.clamp(a, -1.0, 1.0))[0]["obs"].clone()
+            o, r, d, infos = env.step(torch.clamp(a, -1.0, 1.0))
+            if game_meter:
+                meter_record(r, d, infos)
+            obs = o["obs"].clone()
         torch.cuda.synchronize()
     # (fused update behind a captured rollout: the observations are recorded straight into the update's env-major flat batch, below)
     direct_obs = fused is not None and graph_rollout
@@ -382,6 +418,8 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
             if recorder is not None:
                 act = recorder.pre(mu, value, torch.randn_like(mu), g_obs, g_dones)
                 o, r, d, infos = env.step(act)
+                if game_meter:
+                    meter_record(r, d, infos)
                 st = infos.get("stacked_rewards")
                 recorder.post(r, value, infos.get("time_outs"), st if st is not None and st.is_contiguous() else None, d, o["obs"], g_terms, g_dones, g_obs)
                 g_n.add_(1)
@@ -391,6 +429,8 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
             for k, v in (("obs", g_obs), ("act", a), ("mu", mu), ("neglogp", neglogp(a, mu, sigma, logstd)), ("val", value), ("done", g_dones)):
                 mb[k].index_copy_(0, g_n, v.unsqueeze(0))
             o, r, d, infos = env.step(torch.clamp(a, -1.0, 1.0))
+            if game_meter:
+                meter_record(r, d, infos)
             r = r.unsqueeze(1) * c["reward_scale"]
             if c["value_bootstrap"] and "time_outs" in infos:
                 r = r + c["gamma"] * value * infos["time_outs"].unsqueeze(1).float()
@@ -448,6 +488,8 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
                 _sync(device); ts = time.perf_counter()
                 o, r, d, infos = env.step(torch.clamp(a, -1.0, 1.0))            # clip_actions (:467-478)
                 _sync(device); step_time += time.perf_counter() - ts
+                if game_meter:
+                    meter_record(r, d, infos)
                 r = r.unsqueeze(1) * c["reward_scale"]
                 if c["value_bootstrap"] and "time_outs" in infos:               # :656-659
                     r = r + c["gamma"] * value * infos["time_outs"].unsqueeze(1).float()
@@ -625,6 +667,8 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
                                 for f in falls]
             for f, path in zip(falls, s["trace_falls"]):
                 write_npz(path, f)
+        if game_meter:
+            s["game_meter"] = meter[0].summary()
         stats.append(s)
         if rank == 0:
             log("epoch %(epoch)d: fps step %(step_fps).3g  step+inference %(play_fps).3g  total %(total_fps).3g  mean reward %(mean_reward).3f  "
@@ -632,9 +676,27 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
             if epstats is not None:
                 from isaacgymdyros_amd.episode_stats import format_line
                 log("epoch %d: %s" % (ep, format_line(s["episode_stats"])))
-        if nn_dir and rank == 0 and save_frequency > 0 and ep % save_frequency == 0:
+            if game_meter:
+                log("epoch %d: %s" % (ep, GM.format_line(s["game_meter"])))
+        if game_meter:
+            should_exit = False
+            if best is not None and s["game_meter"]["current_size"] > 0:          # a2c_common_dyros.py:1018
+                files, should_exit = best.after_epoch(ep, s["game_meter"]["mean_reward"])
+                for f in files:
+                    save(os.path.join(nn_dir, f + ".pth"), ep, last_mean_rewards=best.last_mean_rewards)
+            if world > 1:          # (rank 0's meter decides for every rank: a2c_common_dyros.py:1078-1081)
+                import torch.distributed as dist
+                flag = torch.tensor([1.0 if should_exit else 0.0], device=device)
+                dist.broadcast(flag, 0)
+                should_exit = bool(flag.item())
+            if should_exit:
+                break
+        elif nn_dir and rank == 0 and save_frequency > 0 and ep % save_frequency == 0:
             save(os.path.join(nn_dir, "%s_%d.pth" % (experiment, ep)), ep)
-    if nn_dir and rank == 0:
+    if best is not None:
+        save(os.path.join(nn_dir, best.final(ep, stats[-1]["game_meter"]["mean_reward"] if stats else 0.0) + ".pth"), ep,
+             last_mean_rewards=best.last_mean_rewards)
+    elif nn_dir and rank == 0:
         save(os.path.join(nn_dir, experiment + ".pth"), ep)
     if own_env:
         env.close()
@@ -653,6 +715,8 @@ def main():
     ap.add_argument("--output-dir", default=None, help="write checkpoints to <dir>/DyrosDynamicWalk/nn/ (rank 0)")
     ap.add_argument("--save-frequency", type=int, default=None, help="epochs between numbered checkpoints (default: the yaml's 100 with --output-dir)")
     ap.add_argument("--episode-stats", action="store_true", help="on-GPU termination causes and episode statistics, one log line per epoch")
+    ap.add_argument("--game-meter", action="store_true", help="on-GPU episode-return meter over the last 100 games (the reference's game_rewards), one "
+                    "log line per epoch; with --output-dir the reference's best-reward and last_* checkpoint names (isaacgymdyros_amd/game_meter.py)")
     ap.add_argument("--trace-falls", default=None, metavar="DIR", help="on-GPU run trace of envs 0..63, frozen at falls: up to 8 falls per epoch "
                     "are written to DIR as .npz (isaacgymdyros_amd/run_trace.py)")
     a = ap.parse_args()
@@ -662,7 +726,8 @@ def main():
     dev = "cuda:%d" % local_rank
     torch.cuda.set_device(local_rank)
     train(a.num_envs, a.epochs, a.horizon, device=dev, rank=rank, world=world, graph_rollout=a.fused, fused_update=a.fused,
-          checkpoint=a.checkpoint, output_dir=a.output_dir, save_frequency=save_frequency, episode_stats=a.episode_stats, trace_falls=a.trace_falls)
+          checkpoint=a.checkpoint, output_dir=a.output_dir, save_frequency=save_frequency, episode_stats=a.episode_stats, trace_falls=a.trace_falls,
+          game_meter=a.game_meter)
     if world > 1:
         torch.distributed.destroy_process_group()
 

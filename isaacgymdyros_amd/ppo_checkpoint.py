@@ -9,7 +9,8 @@ get_full_state_weights -> get_weights -> get_stats_weights):
   epoch               the epochs completed
   optimizer_actor     separate_opt: Adam(actor_mlp + mu), lr the schedule's; Adam(critic_mlp + value), lr 5e-4; eps 1e-8
   optimizer_critic    (a2c_continuous_seperate.py:50-54).  torch.optim.Adam state_dicts: a plain Adam over those parameters loads them and steps
-  frame, last_mean_rewards (-100500 by default), env_state (None: the env keeps no state the reference saves)
+  frame, last_mean_rewards (-100500 by default; the best mean episode return so far when the learner runs its game meter,
+                      isaacgymdyros_amd/game_meter.py), env_state (None: the env keeps no state the reference saves)
   isaacgymdyros_amd   what the reference does not save: the learning-rate schedule (lr0, lr_min, max_epochs), sigma_init / sigma_last and the
                       backend that wrote the file.  The reference's restore (set_full_state_weights) reads keys by name and ignores it.
 MODEL_KEYS' order is the module registration order of network_builder_dyros.py:14-127: state_dict lists a module's direct parameters before its
@@ -43,6 +44,8 @@ GROWTH_FACTOR, BACKOFF_FACTOR, GROWTH_INTERVAL = 2.0, 0.5, 2000
 CRITIC_LR = 5e-4
 # cfg/train/DyrosDynamicWalkPPO.yaml: params.config.save_frequency, and the experiment name its `name` resolves to
 SAVE_FREQUENCY = 100
+SAVE_BEST_AFTER = 200          # params.config.save_best_after
+SCORE_TO_WIN = 20000           # params.config.score_to_win
 NAME = "DyrosDynamicWalk"
 
 
