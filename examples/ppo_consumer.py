@@ -235,7 +235,7 @@ TRACE_DRAIN = 8          # held slots of the run trace written per epoch (train(
 def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cfg=None, max_epochs=None, env=None,
           rank=0, world=1, seed=42, graph_rollout=False, graph_update=False, fused_update=False, fused_collective=None, global_gate=False,
           checkpoint=None, output_dir=None, save_frequency=0, experiment="DyrosDynamicWalk", episode_stats=False, trace_falls=None,
-          game_meter=False, save_best_after=None, score_to_win=None, games_to_track=100):
+          game_meter=False, save_best_after=None, score_to_win=None, games_to_track=100, gait_profile=None):
     """`epochs` PPO epochs of the DYROS configuration on `num_envs` envs of this rank.  Returns one stats dict per epoch.
     graph_rollout: one rollout step (policy inference, sampling, env step, bookkeeping) is captured once in a hipGraph and
     replayed `horizon` times per epoch -- possible because dw_step_dev keeps the step counter in device memory, so a replayed
@@ -275,7 +275,11 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
     at least save_best_after (None: the yaml's 200), <experiment>_ep_<n>_rew_<r>.pth and the end of the run past score_to_win (None: the
     yaml's 20000), and last_<experiment>ep<n>rew<r>.pth, the run's last state, at the end.  The files carry last_mean_rewards, and a
     checkpoint's value is where the best starts, so a resumed run keeps its best.  Sharded, rank 0's meter decides, as in the reference.
-    Off: nothing changes."""
+    Off: nothing changes.
+    gait_profile: True or a cfg sim.mi355.gait_profile dict.  The env's on-GPU gait profile (isaacgymdyros_amd/gait_profile.py, DESIGN.md
+    section 20; its launch sits inside the captured rollout step too) bins sole forces, contacts and the paid foot_contact_reward by mocap
+    phase; every epoch is one window: its summary goes into the epoch's stats dict as "gait_profile" and one more log line gives the paid
+    fraction and the force error per gait window.  Off: neither the dicts nor the log change."""
     from isaacgymdyros_amd.config import default_cfg
     from isaacgymdyros_amd.dyros_dynamic_walk import DyrosDynamicWalk
     cfg = cfg or TRAIN_CFG
@@ -290,6 +294,8 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
             ecfg["sim"]["mi355"]["episode_stats"] = True
         if trace_falls:
             ecfg["sim"]["mi355"]["run_trace"] = {"env_ids": min(64, num_envs), "depth": 512, "hold": "fall"}
+        if gait_profile:
+            ecfg["sim"]["mi355"]["gait_profile"] = gait_profile
         if graph_rollout:
             ecfg["sim"]["mi355"]["device_step_counter"] = True
             ecfg["sim"]["mi355"]["alias_obs"] = True          # (the loop copies what it keeps)
@@ -301,6 +307,9 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
     trace = getattr(env, "run_trace", None) if trace_falls else None
     if trace_falls and trace is None:
         raise ValueError("trace_falls needs an env built with cfg sim.mi355.run_trace")
+    gait = getattr(env, "gait_profile", None) if gait_profile else None
+    if gait_profile and gait is None:
+        raise ValueError("gait_profile needs an env built with cfg sim.mi355.gait_profile")
     torch.manual_seed(seed)                          # same initial weights on every rank
     net = DyrosActorCritic(env.num_obs, env.num_acts, cfg["network"]).to(device)
     torch.manual_seed(seed + 7919 * rank)            # ... but its own exploration noise (Normal.sample draws from the global generator)
@@ -669,6 +678,9 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
                 write_npz(path, f)
         if game_meter:
             s["game_meter"] = meter[0].summary()
+        if gait is not None:
+            s["gait_profile"] = gait.summary()
+            gait.reset_totals()
         stats.append(s)
         if rank == 0:
             log("epoch %(epoch)d: fps step %(step_fps).3g  step+inference %(play_fps).3g  total %(total_fps).3g  mean reward %(mean_reward).3f  "
@@ -678,6 +690,9 @@ def train(num_envs=16384, epochs=2, horizon=None, device="cuda:0", log=print, cf
                 log("epoch %d: %s" % (ep, format_line(s["episode_stats"])))
             if game_meter:
                 log("epoch %d: %s" % (ep, GM.format_line(s["game_meter"])))
+            if gait is not None:
+                from isaacgymdyros_amd.gait_profile import format_line as gait_line
+                log("epoch %d: %s" % (ep, gait_line(s["gait_profile"])))
         if game_meter:
             should_exit = False
             if best is not None and s["game_meter"]["current_size"] > 0:          # a2c_common_dyros.py:1018
@@ -719,6 +734,8 @@ def main():
                     "log line per epoch; with --output-dir the reference's best-reward and last_* checkpoint names (isaacgymdyros_amd/game_meter.py)")
     ap.add_argument("--trace-falls", default=None, metavar="DIR", help="on-GPU run trace of envs 0..63, frozen at falls: up to 8 falls per epoch "
                     "are written to DIR as .npz (isaacgymdyros_amd/run_trace.py)")
+    ap.add_argument("--gait-profile", action="store_true", help="on-GPU gait profile binned by mocap phase, one log line per epoch: the fraction of "
+                    "steps foot_contact_reward is paid and the sole force error per gait window (isaacgymdyros_amd/gait_profile.py)")
     a = ap.parse_args()
     save_frequency = a.save_frequency if a.save_frequency is not None else (100 if a.output_dir else 0)
     from isaacgymdyros_amd import dist as dwdist
@@ -727,7 +744,7 @@ def main():
     torch.cuda.set_device(local_rank)
     train(a.num_envs, a.epochs, a.horizon, device=dev, rank=rank, world=world, graph_rollout=a.fused, fused_update=a.fused,
           checkpoint=a.checkpoint, output_dir=a.output_dir, save_frequency=save_frequency, episode_stats=a.episode_stats, trace_falls=a.trace_falls,
-          game_meter=a.game_meter)
+          game_meter=a.game_meter, gait_profile=a.gait_profile)
     if world > 1:
         torch.distributed.destroy_process_group()
 

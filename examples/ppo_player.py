@@ -15,6 +15,10 @@ end on its own.
 0 .. --trace-envs - 1.  With --trace-hold fall (the default) or reset a slot freezes at the step that ends its episode; after each round of games
 the held slots are written to DIR/fall_env<id>_<n>.npz and armed again, and the count is printed at the end.  With never the rings are written
 once at the end, as DIR/ring_env<id>.npz.
+
+--gait-report turns the on-GPU gait profile on (isaacgymdyros_amd/gait_profile.py) and prints, after playing, the mean
+vertical sole force per foot in the reward's three gait windows beside the mocap force columns, and how often foot_contact_reward was paid.
+--gait-dir DIR also writes the per-bin profile as DIR/gait_profile.npz and DIR/gait_profile.txt; --gait-bins sets the number of phase bins.
 """
 from __future__ import annotations
 
@@ -59,6 +63,8 @@ def run(args):
     if args.trace_dir:
         cfg["sim"]["mi355"]["run_trace"] = {"env_ids": min(args.trace_envs, args.num_envs), "depth": args.trace_depth, "hold": args.trace_hold}
         os.makedirs(args.trace_dir, exist_ok=True)
+    if args.gait_report or args.gait_dir:
+        cfg["sim"]["mi355"]["gait_profile"] = {"bins": args.gait_bins}
     env = DyrosDynamicWalk(cfg, args.device, 0, True)
     traces_written = 0
     ck = PK.load(args.checkpoint)
@@ -102,6 +108,14 @@ def run(args):
                 env.run_trace.save_npz(os.path.join(args.trace_dir, "ring_env%d.npz" % e), e)
             traces_written = len(env.run_trace.env_ids)
         print("run trace: %d files written to %s" % (traces_written, args.trace_dir), flush=True)
+    if env.gait_profile is not None:
+        from isaacgymdyros_amd import gait_profile as GP
+        gs = env.gait_profile.summary()
+        print(GP.format_table(gs), flush=True)
+        if args.gait_dir:
+            txt = GP.write_txt(args.gait_dir, gs)          # (creates the directory)
+            GP.write_npz(os.path.join(args.gait_dir, "gait_profile.npz"), gs)
+            print("gait profile: written to %s and %s" % (os.path.join(args.gait_dir, "gait_profile.npz"), txt), flush=True)
     env.close()
     if games_played == 0:
         raise SystemExit("no game ended within --max-steps %d" % args.max_steps)
@@ -128,6 +142,9 @@ def main():
     ap.add_argument("--trace-depth", type=int, default=512, help="steps kept per traced env")
     ap.add_argument("--trace-hold", default="fall", choices=["never", "fall", "reset"],
                     help="freeze a slot at the step that ends its episode: other than by the time limit / at any reset / never")
+    ap.add_argument("--gait-report", action="store_true", help="collect the on-GPU gait profile and print its three-window table at the end")
+    ap.add_argument("--gait-dir", default=None, help="turn the gait profile on and write gait_profile.npz and gait_profile.txt here")
+    ap.add_argument("--gait-bins", type=int, default=72, choices=[12, 24, 36, 72, 144], help="phase bins of the gait profile")
     ap.add_argument("--device", default="cuda:0")
     run(ap.parse_args())
 

@@ -107,6 +107,9 @@ def validate_cfg(cfg: dict) -> None:
     if sim.get("mi355", {}).get("run_trace") is not None:
         from .run_trace import validate as validate_run_trace          # (env ids in range and distinct, depth, hold mode, ring size)
         validate_run_trace(sim["mi355"]["run_trace"], n)
+    if sim.get("mi355", {}).get("gait_profile") is not None:
+        from .gait_profile import validate as validate_gait_profile          # (bins one of 12, 24, 36, 72, 144; the two filters)
+        validate_gait_profile(sim["mi355"]["gait_profile"])
     iters = int(px.get("num_position_iterations", 4)) + int(px.get("num_velocity_iterations", 1))
     if not 1 <= iters <= 64:
         raise ValueError("physx.num_position_iterations + num_velocity_iterations must be in 1..64")

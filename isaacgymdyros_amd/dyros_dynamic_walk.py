@@ -110,6 +110,14 @@ class DyrosDynamicWalk(VecTask):
         if spec is not None and spec is not False:          # (as validate_cfg reads it: {} is the default trace)
             from .run_trace import RunTrace
             self.run_trace = RunTrace(self, spec)
+        # cfg sim.mi355.gait_profile: sole forces, contacts, the paid foot_contact_reward and the leg joints' tracking binned by mocap phase on
+        # the device, one launch after every step (isaacgymdyros_amd/gait_profile.py); off: None, and step() makes no
+        # extra launch
+        self.gait_profile = None
+        spec = self.cfg["sim"].get("mi355", {}).get("gait_profile")
+        if spec is not None and spec is not False:
+            from .gait_profile import GaitProfile
+            self.gait_profile = GaitProfile(self, spec)
 
     # ------------------------------------------------------------------ native handle
     def _make_config(self):
@@ -384,6 +392,8 @@ class DyrosDynamicWalk(VecTask):
             self.episode_stats.record()          # (fills extras["termination_cause"] in place)
         if self.run_trace is not None:
             self.run_trace.record()
+        if self.gait_profile is not None:
+            self.gait_profile.record()
         self.obs_dict["obs"] = (self.obs_buf if fresh else self._clip_obs(self.obs_buf)).to(self.rl_device)
         return self.obs_dict, self.rew_buf.to(self.rl_device), self.reset_buf.to(self.rl_device), self.extras
 
