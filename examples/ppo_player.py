@@ -19,6 +19,10 @@ once at the end, as DIR/ring_env<id>.npz.
 --gait-report turns the on-GPU gait profile on (isaacgymdyros_amd/gait_profile.py) and prints, after playing, the mean
 vertical sole force per foot in the reward's three gait windows beside the mocap force columns, and how often foot_contact_reward was paid.
 --gait-dir DIR also writes the per-bin profile as DIR/gait_profile.npz and DIR/gait_profile.txt; --gait-bins sets the number of phase bins.
+
+--bodies-dir DIR turns the rigid-body state tensor on (isaacgymdyros_amd/body_states.py) and records envs
+0 .. --bodies-envs - 1 at every step; at the end it writes DIR/bodies_env<id>.npz with names, parents, dt, states [T, 38, 13] (position,
+quaternion xyzw, linear and angular velocity of every body in the world frame) and com [T, 7]: the file an external viewer reads.
 """
 from __future__ import annotations
 
@@ -65,8 +69,16 @@ def run(args):
         os.makedirs(args.trace_dir, exist_ok=True)
     if args.gait_report or args.gait_dir:
         cfg["sim"]["mi355"]["gait_profile"] = {"bins": args.gait_bins}
+    if args.bodies_dir:
+        cfg["sim"]["mi355"]["body_states"] = {"auto": True}
+        os.makedirs(args.bodies_dir, exist_ok=True)
     env = DyrosDynamicWalk(cfg, args.device, 0, True)
     traces_written = 0
+    bodies_k = min(max(args.bodies_envs, 1), args.num_envs) if args.bodies_dir else 0
+    if bodies_k:          # (preallocated: a step adds two device-to-device copies and no host sync)
+        rec_states = torch.zeros(args.max_steps, bodies_k, 38, 13, device=dev)
+        rec_com = torch.zeros(args.max_steps, bodies_k, 7, device=dev)
+    played = 0
     ck = PK.load(args.checkpoint)
     n_obs, n_act = int(ck["model"][PK.PREFIX + "actor_mlp.0.weight"].shape[1]), int(ck["model"][PK.PREFIX + "mu.weight"].shape[0])
     if (n_obs, n_act) != (env.num_obs, env.num_acts):
@@ -83,6 +95,10 @@ def run(args):
         action, _mu = pol.play(obs.contiguous(), noise)
         o, r, done, _info = env.step(action)
         obs = o["obs"]
+        if bodies_k:
+            rec_states[_n].copy_(env.body_states.states[:bodies_k])
+            rec_com[_n].copy_(env.body_states.com[:bodies_k])
+        played = _n + 1
         cr += r.view(N)
         steps += 1
         idx = done.nonzero(as_tuple=False).view(-1)
@@ -116,6 +132,13 @@ def run(args):
             txt = GP.write_txt(args.gait_dir, gs)          # (creates the directory)
             GP.write_npz(os.path.join(args.gait_dir, "gait_profile.npz"), gs)
             print("gait profile: written to %s and %s" % (os.path.join(args.gait_dir, "gait_profile.npz"), txt), flush=True)
+    if bodies_k:
+        import numpy as np
+        bs = env.body_states
+        for e in range(bodies_k):
+            np.savez(os.path.join(args.bodies_dir, "bodies_env%d.npz" % e), names=np.asarray(bs.names), parents=np.asarray(bs.parents, np.int32),
+                     dt=np.float64(bs.dt), states=rec_states[:played, e].cpu().numpy(), com=rec_com[:played, e].cpu().numpy())
+        print("body states: %d steps of %d envs written to %s" % (played, bodies_k, args.bodies_dir), flush=True)
     env.close()
     if games_played == 0:
         raise SystemExit("no game ended within --max-steps %d" % args.max_steps)
@@ -145,6 +168,8 @@ def main():
     ap.add_argument("--gait-report", action="store_true", help="collect the on-GPU gait profile and print its three-window table at the end")
     ap.add_argument("--gait-dir", default=None, help="turn the gait profile on and write gait_profile.npz and gait_profile.txt here")
     ap.add_argument("--gait-bins", type=int, default=72, choices=[12, 24, 36, 72, 144], help="phase bins of the gait profile")
+    ap.add_argument("--bodies-dir", default=None, help="turn the rigid-body state tensor on and write bodies_env<id>.npz (every body's trajectory) here")
+    ap.add_argument("--bodies-envs", type=int, default=1, help="record envs 0 .. K-1")
     ap.add_argument("--device", default="cuda:0")
     run(ap.parse_args())
 

@@ -110,6 +110,9 @@ def validate_cfg(cfg: dict) -> None:
     if sim.get("mi355", {}).get("gait_profile") is not None:
         from .gait_profile import validate as validate_gait_profile          # (bins one of 12, 24, 36, 72, 144; the two filters)
         validate_gait_profile(sim["mi355"]["gait_profile"])
+    if sim.get("mi355", {}).get("body_states") is not None:
+        from .body_states import validate as validate_body_states          # (True / False, or bodies by name or Gym id, com, auto)
+        validate_body_states(sim["mi355"]["body_states"])
     iters = int(px.get("num_position_iterations", 4)) + int(px.get("num_velocity_iterations", 1))
     if not 1 <= iters <= 64:
         raise ValueError("physx.num_position_iterations + num_velocity_iterations must be in 1..64")

@@ -118,6 +118,13 @@ class DyrosDynamicWalk(VecTask):
         if spec is not None and spec is not False:
             from .gait_profile import GaitProfile
             self.gait_profile = GaitProfile(self, spec)
+        # cfg sim.mi355.body_states: the rigid-body state tensor [N, K, 13] and the centre of mass, one launch per refresh
+        # (isaacgymdyros_amd/body_states.py); off: None, no buffer, and step() makes no extra launch
+        self.body_states = None
+        spec = self.cfg["sim"].get("mi355", {}).get("body_states")
+        if spec is not None and spec is not False:
+            from .body_states import BodyStates
+            self.body_states = BodyStates(self, spec)
 
     # ------------------------------------------------------------------ native handle
     def _make_config(self):
@@ -390,6 +397,8 @@ class DyrosDynamicWalk(VecTask):
             self.extras["stacked_rewards"] = log
         if self.episode_stats is not None:
             self.episode_stats.record()          # (fills extras["termination_cause"] in place)
+        if self.body_states is not None and self.body_states.auto:
+            self.body_states.refresh()
         if self.run_trace is not None:
             self.run_trace.record()
         if self.gait_profile is not None:
@@ -408,7 +417,21 @@ class DyrosDynamicWalk(VecTask):
             self.episode_stats.restart(ids)          # (the running episodes of these envs are discarded, not counted)
         if self.run_trace is not None:
             self.run_trace.arm(ids)
+        if self.body_states is not None and self.body_states.auto:
+            self.body_states.refresh()
         # (reset_idx does not touch the observations: the reference recomputes them in the next step's post-physics, :655-669)
+
+    def reset(self):
+        d = super().reset()
+        if self.body_states is not None and self.body_states.auto:
+            self.body_states.refresh()
+        return d
+
+    def refresh_rigid_body_state_tensor(self):
+        """Isaac Gym's call: one launch that brings env.body_states.states (and .com) up to date with root_states and dof_state."""
+        if self.body_states is None:
+            raise RuntimeError("refresh_rigid_body_state_tensor: set cfg sim.mi355.body_states to use the rigid-body state tensor")
+        return self.body_states.refresh()
 
     def _current_step(self) -> int:
         """The step index that keys the in-kernel RNG.  With cfg sim.mi355.device_step_counter the truth is the device word:

@@ -163,6 +163,9 @@ def compile_mjcf(xml_path: str) -> Dict:
             mv_axis.append(ax.tolist())
             mv_range.append(b["range"])
         else:
+            # a jointless body (the four foot bodies) sits on its parent with no offset and no rotation: the rigid-body state tensor
+            # (include/dyros_bodies.h) gives it its carrier's pose
+            assert not np.any(p) and np.array_equal(R, np.eye(3)), (b["name"], b["pos"], b["quat"])
             Rp, pp = T_in_moving[b["parent"]]
             moving_of_body[i] = moving_of_body[b["parent"]]
             T_in_moving[i] = (Rp @ R, pp + Rp @ p)

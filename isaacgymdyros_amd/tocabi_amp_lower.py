@@ -175,6 +175,11 @@ class TocabiAMPLower(VecTask):
         self._amp_stats_on = cfg["sim"].get("mi355", {}).get("amp_episode_stats", False)
         if not isinstance(self._amp_stats_on, bool):
             raise ValueError("sim.mi355.amp_episode_stats must be True or False")
+        # cfg sim.mi355.amp_body_states: the rigid-body state tensor over the physics host's bound buffers (isaacgymdyros_amd/body_states.py,
+        # DESIGN.md section 21); off: None.  This class' own key for the same reason: `body_states` would reach the physics host
+        self._amp_bodies_spec = cfg["sim"].get("mi355", {}).get("amp_body_states")
+        from .body_states import validate as validate_body_states
+        validate_body_states(self._amp_bodies_spec)
         e["numObservations"] = (NUM_OBS + NUM_ACTIONS) * self.num_obs_his - NUM_ACTIONS            # :83
         e["numActions"] = NUM_ACTIONS
         super().__init__(config=cfg, sim_device=sim_device, graphics_device_id=graphics_device_id, headless=headless)
@@ -185,7 +190,7 @@ class TocabiAMPLower(VecTask):
         pc["sim"].update({k: copy.deepcopy(v) for k, v in cfg["sim"].items() if k != "mi355"})
         # (physx.num_position_iterations + num_velocity_iterations = the contact solver's iteration count, as the task yaml gives them:
         #  4 + 0 for this task, cfg/task/TocabiAMPLower.yaml)
-        pc["sim"]["mi355"].update({k: v for k, v in cfg["sim"].get("mi355", {}).items() if k != "amp_episode_stats"})
+        pc["sim"]["mi355"].update({k: v for k, v in cfg["sim"].get("mi355", {}).items() if k not in ("amp_episode_stats", "amp_body_states")})
         pc["env"]["perturbation"] = False
         # spawn height: the reference's 0.89 (:394) puts the soles 2.2 cm INTO the plane in the initial pose; PhysX resolves that
         # positionally, this simulator's contact model through a velocity bias (erp), which launches the robot at 2 m/s.  Default
@@ -354,6 +359,10 @@ class TocabiAMPLower(VecTask):
             from .amp_episode_stats import AmpEpisodeStats
             self.episode_stats = AmpEpisodeStats(self)
             self.extras["termination_cause"] = self.episode_stats.cause
+        self.body_states = None
+        if self._amp_bodies_spec is not None and self._amp_bodies_spec is not False:
+            from .body_states import BodyStates
+            self.body_states = BodyStates(self._phys, self._amp_bodies_spec)          # (vel_at_com: the physics host's root_vel_at_com)
 
     # ------------------------------------------------------------------ helpers
     def _rand(self, *shape):
@@ -945,7 +954,15 @@ class TocabiAMPLower(VecTask):
         out = self._step_fused(actions) if self._fused else self._step_torch(actions)
         if self.episode_stats is not None:
             self.episode_stats.record()          # (fills extras["termination_cause"] in place; every step form ends here)
+        if self.body_states is not None and self.body_states.auto:
+            self.body_states.refresh()
         return out
+
+    def refresh_rigid_body_state_tensor(self):
+        """Isaac Gym's call: one launch that brings amp.body_states.states (and .com) up to date with the physics' buffers."""
+        if self.body_states is None:
+            raise RuntimeError("refresh_rigid_body_state_tensor: set cfg sim.mi355.amp_body_states to use the rigid-body state tensor")
+        return self.body_states.refresh()
 
     def _step_torch(self, actions):
         action_tensor = torch.clamp(actions, -self.clip_actions, self.clip_actions)
