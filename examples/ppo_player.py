@@ -23,6 +23,10 @@ vertical sole force per foot in the reward's three gait windows beside the mocap
 --bodies-dir DIR turns the rigid-body state tensor on (isaacgymdyros_amd/body_states.py) and records envs
 0 .. --bodies-envs - 1 at every step; at the end it writes DIR/bodies_env<id>.npz with names, parents, dt, states [T, 38, 13] (position,
 quaternion xyzw, linear and angular velocity of every body in the world frame) and com [T, 7]: the file an external viewer reads.
+
+--sensors-dir DIR turns the foot force-torque sensors on (isaacgymdyros_amd/force_sensors.py) and records envs
+0 .. --sensors-envs - 1 at every step; at the end it writes DIR/sensors_env<id>.npz with names, dt, sensors [T, S, 6] (force then torque of the
+ground on each foot, in the sensor frame), cop [T, 2, 4] (x, y in the foot frame, Fz, loaded corners) and zmp [T, 4].
 """
 from __future__ import annotations
 
@@ -72,12 +76,20 @@ def run(args):
     if args.bodies_dir:
         cfg["sim"]["mi355"]["body_states"] = {"auto": True}
         os.makedirs(args.bodies_dir, exist_ok=True)
+    if args.sensors_dir:
+        cfg["sim"]["mi355"]["force_sensors"] = {"auto": True}
+        os.makedirs(args.sensors_dir, exist_ok=True)
     env = DyrosDynamicWalk(cfg, args.device, 0, True)
     traces_written = 0
     bodies_k = min(max(args.bodies_envs, 1), args.num_envs) if args.bodies_dir else 0
     if bodies_k:          # (preallocated: a step adds two device-to-device copies and no host sync)
         rec_states = torch.zeros(args.max_steps, bodies_k, 38, 13, device=dev)
         rec_com = torch.zeros(args.max_steps, bodies_k, 7, device=dev)
+    sensors_k = min(max(args.sensors_envs, 1), args.num_envs) if args.sensors_dir else 0
+    if sensors_k:
+        rec_sen = torch.zeros(args.max_steps, sensors_k, len(env.force_sensors.names), 6, device=dev)
+        rec_cop = torch.zeros(args.max_steps, sensors_k, 2, 4, device=dev)
+        rec_zmp = torch.zeros(args.max_steps, sensors_k, 4, device=dev)
     played = 0
     ck = PK.load(args.checkpoint)
     n_obs, n_act = int(ck["model"][PK.PREFIX + "actor_mlp.0.weight"].shape[1]), int(ck["model"][PK.PREFIX + "mu.weight"].shape[0])
@@ -98,6 +110,10 @@ def run(args):
         if bodies_k:
             rec_states[_n].copy_(env.body_states.states[:bodies_k])
             rec_com[_n].copy_(env.body_states.com[:bodies_k])
+        if sensors_k:
+            rec_sen[_n].copy_(env.force_sensors.sensors[:sensors_k])
+            rec_cop[_n].copy_(env.force_sensors.cop[:sensors_k])
+            rec_zmp[_n].copy_(env.force_sensors.zmp[:sensors_k])
         played = _n + 1
         cr += r.view(N)
         steps += 1
@@ -139,6 +155,13 @@ def run(args):
             np.savez(os.path.join(args.bodies_dir, "bodies_env%d.npz" % e), names=np.asarray(bs.names), parents=np.asarray(bs.parents, np.int32),
                      dt=np.float64(bs.dt), states=rec_states[:played, e].cpu().numpy(), com=rec_com[:played, e].cpu().numpy())
         print("body states: %d steps of %d envs written to %s" % (played, bodies_k, args.bodies_dir), flush=True)
+    if sensors_k:
+        import numpy as np
+        fs = env.force_sensors
+        for e in range(sensors_k):
+            np.savez(os.path.join(args.sensors_dir, "sensors_env%d.npz" % e), names=np.asarray(fs.names), dt=np.float64(fs.dt),
+                     sensors=rec_sen[:played, e].cpu().numpy(), cop=rec_cop[:played, e].cpu().numpy(), zmp=rec_zmp[:played, e].cpu().numpy())
+        print("force sensors: %d steps of %d envs written to %s" % (played, sensors_k, args.sensors_dir), flush=True)
     env.close()
     if games_played == 0:
         raise SystemExit("no game ended within --max-steps %d" % args.max_steps)
@@ -170,6 +193,8 @@ def main():
     ap.add_argument("--gait-bins", type=int, default=72, choices=[12, 24, 36, 72, 144], help="phase bins of the gait profile")
     ap.add_argument("--bodies-dir", default=None, help="turn the rigid-body state tensor on and write bodies_env<id>.npz (every body's trajectory) here")
     ap.add_argument("--bodies-envs", type=int, default=1, help="record envs 0 .. K-1")
+    ap.add_argument("--sensors-dir", default=None, help="turn the foot force-torque sensors on and write sensors_env<id>.npz (wrenches, centres of pressure, ZMP) here")
+    ap.add_argument("--sensors-envs", type=int, default=1, help="record envs 0 .. K-1")
     ap.add_argument("--device", default="cuda:0")
     run(ap.parse_args())
 

@@ -113,6 +113,10 @@ def validate_cfg(cfg: dict) -> None:
     if sim.get("mi355", {}).get("body_states") is not None:
         from .body_states import validate as validate_body_states          # (True / False, or bodies by name or Gym id, com, auto)
         validate_body_states(sim["mi355"]["body_states"])
+    for key in ("force_sensors", "amp_force_sensors"):
+        if sim.get("mi355", {}).get(key) is not None:
+            from .force_sensors import validate as validate_force_sensors          # (sensors on the foot bodies, cop, corners, auto; plane only)
+            validate_force_sensors(sim["mi355"][key], cfg.get("terrain"))
     iters = int(px.get("num_position_iterations", 4)) + int(px.get("num_velocity_iterations", 1))
     if not 1 <= iters <= 64:
         raise ValueError("physx.num_position_iterations + num_velocity_iterations must be in 1..64")

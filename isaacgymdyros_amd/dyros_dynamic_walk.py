@@ -125,6 +125,13 @@ class DyrosDynamicWalk(VecTask):
         if spec is not None and spec is not False:
             from .body_states import BodyStates
             self.body_states = BodyStates(self, spec)
+        # cfg sim.mi355.force_sensors: the foot force-torque sensors [N, S, 6], the soles' centres of pressure and the ZMP, one launch per
+        # refresh (isaacgymdyros_amd/force_sensors.py); off: None, no buffer, and step() makes no extra launch
+        self.force_sensors = None
+        spec = self.cfg["sim"].get("mi355", {}).get("force_sensors")
+        if spec is not None and spec is not False:
+            from .force_sensors import ForceSensors
+            self.force_sensors = ForceSensors(self, spec)
 
     # ------------------------------------------------------------------ native handle
     def _make_config(self):
@@ -399,6 +406,8 @@ class DyrosDynamicWalk(VecTask):
             self.episode_stats.record()          # (fills extras["termination_cause"] in place)
         if self.body_states is not None and self.body_states.auto:
             self.body_states.refresh()
+        if self.force_sensors is not None and self.force_sensors.auto:
+            self.force_sensors.refresh()
         if self.run_trace is not None:
             self.run_trace.record()
         if self.gait_profile is not None:
@@ -419,12 +428,16 @@ class DyrosDynamicWalk(VecTask):
             self.run_trace.arm(ids)
         if self.body_states is not None and self.body_states.auto:
             self.body_states.refresh()
+        if self.force_sensors is not None and self.force_sensors.auto:
+            self.force_sensors.refresh()
         # (reset_idx does not touch the observations: the reference recomputes them in the next step's post-physics, :655-669)
 
     def reset(self):
         d = super().reset()
         if self.body_states is not None and self.body_states.auto:
             self.body_states.refresh()
+        if self.force_sensors is not None and self.force_sensors.auto:
+            self.force_sensors.refresh()
         return d
 
     def refresh_rigid_body_state_tensor(self):
@@ -432,6 +445,13 @@ class DyrosDynamicWalk(VecTask):
         if self.body_states is None:
             raise RuntimeError("refresh_rigid_body_state_tensor: set cfg sim.mi355.body_states to use the rigid-body state tensor")
         return self.body_states.refresh()
+
+    def refresh_force_sensor_tensor(self):
+        """Isaac Gym's call: one launch that brings env.force_sensors up to date with root_states, dof_state and the task record; returns
+        the vec_sensor_tensor view [N, S * 6]."""
+        if self.force_sensors is None:
+            raise RuntimeError("refresh_force_sensor_tensor: set cfg sim.mi355.force_sensors to use the foot force-torque sensors")
+        return self.force_sensors.refresh()
 
     def _current_step(self) -> int:
         """The step index that keys the in-kernel RNG.  With cfg sim.mi355.device_step_counter the truth is the device word:

@@ -180,6 +180,11 @@ class TocabiAMPLower(VecTask):
         self._amp_bodies_spec = cfg["sim"].get("mi355", {}).get("amp_body_states")
         from .body_states import validate as validate_body_states
         validate_body_states(self._amp_bodies_spec)
+        # cfg sim.mi355.amp_force_sensors: the foot force-torque sensors over the physics host's bound buffers (isaacgymdyros_amd/force_sensors.py,
+        # DESIGN.md section 22); off: None.  This class' own key for the same reason
+        self._amp_sensors_spec = cfg["sim"].get("mi355", {}).get("amp_force_sensors")
+        from .force_sensors import validate as validate_force_sensors
+        validate_force_sensors(self._amp_sensors_spec, cfg.get("terrain"))
         e["numObservations"] = (NUM_OBS + NUM_ACTIONS) * self.num_obs_his - NUM_ACTIONS            # :83
         e["numActions"] = NUM_ACTIONS
         super().__init__(config=cfg, sim_device=sim_device, graphics_device_id=graphics_device_id, headless=headless)
@@ -190,7 +195,7 @@ class TocabiAMPLower(VecTask):
         pc["sim"].update({k: copy.deepcopy(v) for k, v in cfg["sim"].items() if k != "mi355"})
         # (physx.num_position_iterations + num_velocity_iterations = the contact solver's iteration count, as the task yaml gives them:
         #  4 + 0 for this task, cfg/task/TocabiAMPLower.yaml)
-        pc["sim"]["mi355"].update({k: v for k, v in cfg["sim"].get("mi355", {}).items() if k not in ("amp_episode_stats", "amp_body_states")})
+        pc["sim"]["mi355"].update({k: v for k, v in cfg["sim"].get("mi355", {}).items() if k not in ("amp_episode_stats", "amp_body_states", "amp_force_sensors")})
         pc["env"]["perturbation"] = False
         # spawn height: the reference's 0.89 (:394) puts the soles 2.2 cm INTO the plane in the initial pose; PhysX resolves that
         # positionally, this simulator's contact model through a velocity bias (erp), which launches the robot at 2 m/s.  Default
@@ -363,6 +368,10 @@ class TocabiAMPLower(VecTask):
         if self._amp_bodies_spec is not None and self._amp_bodies_spec is not False:
             from .body_states import BodyStates
             self.body_states = BodyStates(self._phys, self._amp_bodies_spec)          # (vel_at_com: the physics host's root_vel_at_com)
+        self.force_sensors = None
+        if self._amp_sensors_spec is not None and self._amp_sensors_spec is not False:
+            from .force_sensors import ForceSensors
+            self.force_sensors = ForceSensors(self._phys, self._amp_sensors_spec)
 
     # ------------------------------------------------------------------ helpers
     def _rand(self, *shape):
@@ -956,7 +965,15 @@ class TocabiAMPLower(VecTask):
             self.episode_stats.record()          # (fills extras["termination_cause"] in place; every step form ends here)
         if self.body_states is not None and self.body_states.auto:
             self.body_states.refresh()
+        if self.force_sensors is not None and self.force_sensors.auto:
+            self.force_sensors.refresh()
         return out
+
+    def refresh_force_sensor_tensor(self):
+        """Isaac Gym's call: one launch that brings amp.force_sensors up to date with the physics' buffers."""
+        if self.force_sensors is None:
+            raise RuntimeError("refresh_force_sensor_tensor: set cfg sim.mi355.amp_force_sensors to use the foot force-torque sensors")
+        return self.force_sensors.refresh()
 
     def refresh_rigid_body_state_tensor(self):
         """Isaac Gym's call: one launch that brings amp.body_states.states (and .com) up to date with the physics' buffers."""
