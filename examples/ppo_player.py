@@ -27,6 +27,11 @@ quaternion xyzw, linear and angular velocity of every body in the world frame) a
 --sensors-dir DIR turns the foot force-torque sensors on (isaacgymdyros_amd/force_sensors.py) and records envs
 0 .. --sensors-envs - 1 at every step; at the end it writes DIR/sensors_env<id>.npz with names, dt, sensors [T, S, 6] (force then torque of the
 ground on each foot, in the sensor frame), cop [T, 2, 4] (x, y in the foot frame, Fz, loaded corners) and zmp [T, 4].
+
+--dynamics-dir DIR turns the Jacobian and mass-matrix tensors on (isaacgymdyros_amd/jacobians.py) and records envs
+0 .. --dynamics-envs - 1 at every step; at the end it writes DIR/dynamics_env<id>.npz with names, dof_names, dt, jacobian [T, 3, 6, 39] (head and
+both feet; rows linear then angular, columns the root's linear and angular velocity then the 33 DoFs), mass_matrix [T, 39, 39] and
+com_jacobian [T, 3, 39].
 """
 from __future__ import annotations
 
@@ -79,6 +84,9 @@ def run(args):
     if args.sensors_dir:
         cfg["sim"]["mi355"]["force_sensors"] = {"auto": True}
         os.makedirs(args.sensors_dir, exist_ok=True)
+    if args.dynamics_dir:
+        cfg["sim"]["mi355"]["jacobians"] = {"bodies": ["Head_Link", "L_Foot_Link", "R_Foot_Link"], "com_jacobian": True, "auto": True}
+        os.makedirs(args.dynamics_dir, exist_ok=True)
     env = DyrosDynamicWalk(cfg, args.device, 0, True)
     traces_written = 0
     bodies_k = min(max(args.bodies_envs, 1), args.num_envs) if args.bodies_dir else 0
@@ -90,6 +98,11 @@ def run(args):
         rec_sen = torch.zeros(args.max_steps, sensors_k, len(env.force_sensors.names), 6, device=dev)
         rec_cop = torch.zeros(args.max_steps, sensors_k, 2, 4, device=dev)
         rec_zmp = torch.zeros(args.max_steps, sensors_k, 4, device=dev)
+    dynamics_k = min(max(args.dynamics_envs, 1), args.num_envs) if args.dynamics_dir else 0
+    if dynamics_k:
+        rec_jac = torch.zeros(args.max_steps, dynamics_k, 3, 6, 39, device=dev)
+        rec_mm = torch.zeros(args.max_steps, dynamics_k, 39, 39, device=dev)
+        rec_cj = torch.zeros(args.max_steps, dynamics_k, 3, 39, device=dev)
     played = 0
     ck = PK.load(args.checkpoint)
     n_obs, n_act = int(ck["model"][PK.PREFIX + "actor_mlp.0.weight"].shape[1]), int(ck["model"][PK.PREFIX + "mu.weight"].shape[0])
@@ -114,6 +127,10 @@ def run(args):
             rec_sen[_n].copy_(env.force_sensors.sensors[:sensors_k])
             rec_cop[_n].copy_(env.force_sensors.cop[:sensors_k])
             rec_zmp[_n].copy_(env.force_sensors.zmp[:sensors_k])
+        if dynamics_k:
+            rec_jac[_n].copy_(env.jacobians.jacobian[:dynamics_k])
+            rec_mm[_n].copy_(env.jacobians.mass_matrix[:dynamics_k])
+            rec_cj[_n].copy_(env.jacobians.com_jacobian[:dynamics_k])
         played = _n + 1
         cr += r.view(N)
         steps += 1
@@ -162,6 +179,14 @@ def run(args):
             np.savez(os.path.join(args.sensors_dir, "sensors_env%d.npz" % e), names=np.asarray(fs.names), dt=np.float64(fs.dt),
                      sensors=rec_sen[:played, e].cpu().numpy(), cop=rec_cop[:played, e].cpu().numpy(), zmp=rec_zmp[:played, e].cpu().numpy())
         print("force sensors: %d steps of %d envs written to %s" % (played, sensors_k, args.sensors_dir), flush=True)
+    if dynamics_k:
+        import numpy as np
+        jc = env.jacobians
+        for e in range(dynamics_k):
+            np.savez(os.path.join(args.dynamics_dir, "dynamics_env%d.npz" % e), names=np.asarray(jc.names), dof_names=np.asarray(jc.dof_names),
+                     dt=np.float64(jc.dt), jacobian=rec_jac[:played, e].cpu().numpy(), mass_matrix=rec_mm[:played, e].cpu().numpy(),
+                     com_jacobian=rec_cj[:played, e].cpu().numpy())
+        print("dynamics: %d steps of %d envs written to %s" % (played, dynamics_k, args.dynamics_dir), flush=True)
     env.close()
     if games_played == 0:
         raise SystemExit("no game ended within --max-steps %d" % args.max_steps)
@@ -195,6 +220,8 @@ def main():
     ap.add_argument("--bodies-envs", type=int, default=1, help="record envs 0 .. K-1")
     ap.add_argument("--sensors-dir", default=None, help="turn the foot force-torque sensors on and write sensors_env<id>.npz (wrenches, centres of pressure, ZMP) here")
     ap.add_argument("--sensors-envs", type=int, default=1, help="record envs 0 .. K-1")
+    ap.add_argument("--dynamics-dir", default=None, help="turn the Jacobian and mass-matrix tensors on and write dynamics_env<id>.npz (head and foot Jacobians, M, COM Jacobian) here")
+    ap.add_argument("--dynamics-envs", type=int, default=1, help="record envs 0 .. K-1")
     ap.add_argument("--device", default="cuda:0")
     run(ap.parse_args())
 

@@ -113,6 +113,10 @@ def validate_cfg(cfg: dict) -> None:
     if sim.get("mi355", {}).get("body_states") is not None:
         from .body_states import validate as validate_body_states          # (True / False, or bodies by name or Gym id, com, auto)
         validate_body_states(sim["mi355"]["body_states"])
+    for key in ("jacobians", "amp_jacobians"):
+        if sim.get("mi355", {}).get(key) is not None:
+            from .jacobians import validate as validate_jacobians          # (True / False, or bodies, jacobian, mass_matrix, com_jacobian, armature, auto)
+            validate_jacobians(sim["mi355"][key])
     for key in ("force_sensors", "amp_force_sensors"):
         if sim.get("mi355", {}).get(key) is not None:
             from .force_sensors import validate as validate_force_sensors          # (sensors on the foot bodies, cop, corners, auto; plane only)

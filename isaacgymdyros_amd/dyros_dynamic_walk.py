@@ -132,6 +132,13 @@ class DyrosDynamicWalk(VecTask):
         if spec is not None and spec is not False:
             from .force_sensors import ForceSensors
             self.force_sensors = ForceSensors(self, spec)
+        # cfg sim.mi355.jacobians: the Jacobian tensor [N, K, 6, 39], the mass matrix [N, 39, 39] and the COM Jacobian, one launch per refresh
+        # (isaacgymdyros_amd/jacobians.py); off: None, no buffer, and step() makes no extra launch
+        self.jacobians = None
+        spec = self.cfg["sim"].get("mi355", {}).get("jacobians")
+        if spec is not None and spec is not False:
+            from .jacobians import Jacobians
+            self.jacobians = Jacobians(self, spec)
 
     # ------------------------------------------------------------------ native handle
     def _make_config(self):
@@ -408,6 +415,8 @@ class DyrosDynamicWalk(VecTask):
             self.body_states.refresh()
         if self.force_sensors is not None and self.force_sensors.auto:
             self.force_sensors.refresh()
+        if self.jacobians is not None and self.jacobians.auto:
+            self.jacobians.refresh()
         if self.run_trace is not None:
             self.run_trace.record()
         if self.gait_profile is not None:
@@ -430,6 +439,8 @@ class DyrosDynamicWalk(VecTask):
             self.body_states.refresh()
         if self.force_sensors is not None and self.force_sensors.auto:
             self.force_sensors.refresh()
+        if self.jacobians is not None and self.jacobians.auto:
+            self.jacobians.refresh()
         # (reset_idx does not touch the observations: the reference recomputes them in the next step's post-physics, :655-669)
 
     def reset(self):
@@ -438,6 +449,8 @@ class DyrosDynamicWalk(VecTask):
             self.body_states.refresh()
         if self.force_sensors is not None and self.force_sensors.auto:
             self.force_sensors.refresh()
+        if self.jacobians is not None and self.jacobians.auto:
+            self.jacobians.refresh()
         return d
 
     def refresh_rigid_body_state_tensor(self):
@@ -452,6 +465,18 @@ class DyrosDynamicWalk(VecTask):
         if self.force_sensors is None:
             raise RuntimeError("refresh_force_sensor_tensor: set cfg sim.mi355.force_sensors to use the foot force-torque sensors")
         return self.force_sensors.refresh()
+
+    def refresh_jacobian_tensors(self):
+        """Isaac Gym's call: one launch that brings env.jacobians.jacobian up to date with root_states and dof_state; returns it."""
+        if self.jacobians is None:
+            raise RuntimeError("refresh_jacobian_tensors: set cfg sim.mi355.jacobians to use the Jacobian tensor")
+        return self.jacobians.refresh_jacobian()
+
+    def refresh_mass_matrix_tensors(self):
+        """Isaac Gym's call: one launch that brings env.jacobians.mass_matrix (and .com_jacobian) up to date; returns the mass matrix."""
+        if self.jacobians is None:
+            raise RuntimeError("refresh_mass_matrix_tensors: set cfg sim.mi355.jacobians to use the mass-matrix tensor")
+        return self.jacobians.refresh_mass_matrix()
 
     def _current_step(self) -> int:
         """The step index that keys the in-kernel RNG.  With cfg sim.mi355.device_step_counter the truth is the device word:

@@ -185,6 +185,11 @@ class TocabiAMPLower(VecTask):
         self._amp_sensors_spec = cfg["sim"].get("mi355", {}).get("amp_force_sensors")
         from .force_sensors import validate as validate_force_sensors
         validate_force_sensors(self._amp_sensors_spec, cfg.get("terrain"))
+        # cfg sim.mi355.amp_jacobians: the Jacobian and mass-matrix tensors over the physics host's bound buffers (isaacgymdyros_amd/jacobians.py,
+        # DESIGN.md section 23); off: None.  This class' own key for the same reason
+        self._amp_jacobians_spec = cfg["sim"].get("mi355", {}).get("amp_jacobians")
+        from .jacobians import validate as validate_jacobians
+        validate_jacobians(self._amp_jacobians_spec)
         e["numObservations"] = (NUM_OBS + NUM_ACTIONS) * self.num_obs_his - NUM_ACTIONS            # :83
         e["numActions"] = NUM_ACTIONS
         super().__init__(config=cfg, sim_device=sim_device, graphics_device_id=graphics_device_id, headless=headless)
@@ -195,7 +200,7 @@ class TocabiAMPLower(VecTask):
         pc["sim"].update({k: copy.deepcopy(v) for k, v in cfg["sim"].items() if k != "mi355"})
         # (physx.num_position_iterations + num_velocity_iterations = the contact solver's iteration count, as the task yaml gives them:
         #  4 + 0 for this task, cfg/task/TocabiAMPLower.yaml)
-        pc["sim"]["mi355"].update({k: v for k, v in cfg["sim"].get("mi355", {}).items() if k not in ("amp_episode_stats", "amp_body_states", "amp_force_sensors")})
+        pc["sim"]["mi355"].update({k: v for k, v in cfg["sim"].get("mi355", {}).items() if k not in ("amp_episode_stats", "amp_body_states", "amp_force_sensors", "amp_jacobians")})
         pc["env"]["perturbation"] = False
         # spawn height: the reference's 0.89 (:394) puts the soles 2.2 cm INTO the plane in the initial pose; PhysX resolves that
         # positionally, this simulator's contact model through a velocity bias (erp), which launches the robot at 2 m/s.  Default
@@ -372,6 +377,10 @@ class TocabiAMPLower(VecTask):
         if self._amp_sensors_spec is not None and self._amp_sensors_spec is not False:
             from .force_sensors import ForceSensors
             self.force_sensors = ForceSensors(self._phys, self._amp_sensors_spec)
+        self.jacobians = None
+        if self._amp_jacobians_spec is not None and self._amp_jacobians_spec is not False:
+            from .jacobians import Jacobians
+            self.jacobians = Jacobians(self._phys, self._amp_jacobians_spec)
 
     # ------------------------------------------------------------------ helpers
     def _rand(self, *shape):
@@ -967,7 +976,21 @@ class TocabiAMPLower(VecTask):
             self.body_states.refresh()
         if self.force_sensors is not None and self.force_sensors.auto:
             self.force_sensors.refresh()
+        if self.jacobians is not None and self.jacobians.auto:
+            self.jacobians.refresh()
         return out
+
+    def refresh_jacobian_tensors(self):
+        """Isaac Gym's call: one launch that brings amp.jacobians.jacobian up to date with the physics' buffers."""
+        if self.jacobians is None:
+            raise RuntimeError("refresh_jacobian_tensors: set cfg sim.mi355.amp_jacobians to use the Jacobian tensor")
+        return self.jacobians.refresh_jacobian()
+
+    def refresh_mass_matrix_tensors(self):
+        """Isaac Gym's call: one launch that brings amp.jacobians.mass_matrix (and .com_jacobian) up to date with the physics' buffers."""
+        if self.jacobians is None:
+            raise RuntimeError("refresh_mass_matrix_tensors: set cfg sim.mi355.amp_jacobians to use the mass-matrix tensor")
+        return self.jacobians.refresh_mass_matrix()
 
     def refresh_force_sensor_tensor(self):
         """Isaac Gym's call: one launch that brings amp.force_sensors up to date with the physics' buffers."""
