@@ -31,7 +31,8 @@ ground on each foot, in the sensor frame), cop [T, 2, 4] (x, y in the foot frame
 --dynamics-dir DIR turns the Jacobian and mass-matrix tensors on (isaacgymdyros_amd/jacobians.py) and records envs
 0 .. --dynamics-envs - 1 at every step; at the end it writes DIR/dynamics_env<id>.npz with names, dof_names, dt, jacobian [T, 3, 6, 39] (head and
 both feet; rows linear then angular, columns the root's linear and angular velocity then the 33 DoFs), mass_matrix [T, 39, 39] and
-com_jacobian [T, 3, 39].
+com_jacobian [T, 3, 39].  With --dynamics-forces it also turns the bias-force, gravity and momentum tensors on (isaacgymdyros_amd/dynamics.py,
+DESIGN.md section 24) and adds bias [T, 39], gravity [T, 39] and momentum [T, 6] to each file; without the flag the files are unchanged.
 """
 from __future__ import annotations
 
@@ -86,6 +87,8 @@ def run(args):
         os.makedirs(args.sensors_dir, exist_ok=True)
     if args.dynamics_dir:
         cfg["sim"]["mi355"]["jacobians"] = {"bodies": ["Head_Link", "L_Foot_Link", "R_Foot_Link"], "com_jacobian": True, "auto": True}
+        if args.dynamics_forces:
+            cfg["sim"]["mi355"]["dynamics"] = {"momentum": True, "auto": True}
         os.makedirs(args.dynamics_dir, exist_ok=True)
     env = DyrosDynamicWalk(cfg, args.device, 0, True)
     traces_written = 0
@@ -103,6 +106,11 @@ def run(args):
         rec_jac = torch.zeros(args.max_steps, dynamics_k, 3, 6, 39, device=dev)
         rec_mm = torch.zeros(args.max_steps, dynamics_k, 39, 39, device=dev)
         rec_cj = torch.zeros(args.max_steps, dynamics_k, 3, 39, device=dev)
+    forces = bool(dynamics_k and args.dynamics_forces)
+    if forces:
+        rec_bias = torch.zeros(args.max_steps, dynamics_k, 39, device=dev)
+        rec_grav = torch.zeros(args.max_steps, dynamics_k, 39, device=dev)
+        rec_mom = torch.zeros(args.max_steps, dynamics_k, 6, device=dev)
     played = 0
     ck = PK.load(args.checkpoint)
     n_obs, n_act = int(ck["model"][PK.PREFIX + "actor_mlp.0.weight"].shape[1]), int(ck["model"][PK.PREFIX + "mu.weight"].shape[0])
@@ -131,6 +139,10 @@ def run(args):
             rec_jac[_n].copy_(env.jacobians.jacobian[:dynamics_k])
             rec_mm[_n].copy_(env.jacobians.mass_matrix[:dynamics_k])
             rec_cj[_n].copy_(env.jacobians.com_jacobian[:dynamics_k])
+        if forces:
+            rec_bias[_n].copy_(env.dynamics.bias[:dynamics_k])
+            rec_grav[_n].copy_(env.dynamics.gravity[:dynamics_k])
+            rec_mom[_n].copy_(env.dynamics.momentum[:dynamics_k])
         played = _n + 1
         cr += r.view(N)
         steps += 1
@@ -183,9 +195,12 @@ def run(args):
         import numpy as np
         jc = env.jacobians
         for e in range(dynamics_k):
+            more = {}
+            if forces:
+                more = dict(bias=rec_bias[:played, e].cpu().numpy(), gravity=rec_grav[:played, e].cpu().numpy(), momentum=rec_mom[:played, e].cpu().numpy())
             np.savez(os.path.join(args.dynamics_dir, "dynamics_env%d.npz" % e), names=np.asarray(jc.names), dof_names=np.asarray(jc.dof_names),
                      dt=np.float64(jc.dt), jacobian=rec_jac[:played, e].cpu().numpy(), mass_matrix=rec_mm[:played, e].cpu().numpy(),
-                     com_jacobian=rec_cj[:played, e].cpu().numpy())
+                     com_jacobian=rec_cj[:played, e].cpu().numpy(), **more)
         print("dynamics: %d steps of %d envs written to %s" % (played, dynamics_k, args.dynamics_dir), flush=True)
     env.close()
     if games_played == 0:
@@ -222,6 +237,7 @@ def main():
     ap.add_argument("--sensors-envs", type=int, default=1, help="record envs 0 .. K-1")
     ap.add_argument("--dynamics-dir", default=None, help="turn the Jacobian and mass-matrix tensors on and write dynamics_env<id>.npz (head and foot Jacobians, M, COM Jacobian) here")
     ap.add_argument("--dynamics-envs", type=int, default=1, help="record envs 0 .. K-1")
+    ap.add_argument("--dynamics-forces", action="store_true", help="with --dynamics-dir: add the bias forces, the gravity forces and the momentum to each file")
     ap.add_argument("--device", default="cuda:0")
     run(ap.parse_args())
 

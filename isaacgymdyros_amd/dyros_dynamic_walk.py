@@ -139,6 +139,13 @@ class DyrosDynamicWalk(VecTask):
         if spec is not None and spec is not False:
             from .jacobians import Jacobians
             self.jacobians = Jacobians(self, spec)
+        # cfg sim.mi355.dynamics: the bias-force, gravity, inverse-dynamics and momentum tensors [N, 39] / [N, 6], one launch per call
+        # (isaacgymdyros_amd/dynamics.py); off: None, no buffer, and step() makes no extra launch
+        self.dynamics = None
+        spec = self.cfg["sim"].get("mi355", {}).get("dynamics")
+        if spec is not None and spec is not False:
+            from .dynamics import Dynamics
+            self.dynamics = Dynamics(self, spec)
 
     # ------------------------------------------------------------------ native handle
     def _make_config(self):
@@ -417,6 +424,8 @@ class DyrosDynamicWalk(VecTask):
             self.force_sensors.refresh()
         if self.jacobians is not None and self.jacobians.auto:
             self.jacobians.refresh()
+        if self.dynamics is not None and self.dynamics.auto:
+            self.dynamics.refresh()
         if self.run_trace is not None:
             self.run_trace.record()
         if self.gait_profile is not None:
@@ -441,6 +450,8 @@ class DyrosDynamicWalk(VecTask):
             self.force_sensors.refresh()
         if self.jacobians is not None and self.jacobians.auto:
             self.jacobians.refresh()
+        if self.dynamics is not None and self.dynamics.auto:
+            self.dynamics.refresh()
         # (reset_idx does not touch the observations: the reference recomputes them in the next step's post-physics, :655-669)
 
     def reset(self):
@@ -451,6 +462,8 @@ class DyrosDynamicWalk(VecTask):
             self.force_sensors.refresh()
         if self.jacobians is not None and self.jacobians.auto:
             self.jacobians.refresh()
+        if self.dynamics is not None and self.dynamics.auto:
+            self.dynamics.refresh()
         return d
 
     def refresh_rigid_body_state_tensor(self):
