@@ -121,6 +121,10 @@ def validate_cfg(cfg: dict) -> None:
         if sim.get("mi355", {}).get(key) is not None:
             from .dynamics import validate as validate_dynamics          # (True / False, or bias, gravity, inverse_dynamics, momentum, armature, auto)
             validate_dynamics(sim["mi355"][key])
+    for key in ("forward_dynamics", "amp_forward_dynamics"):
+        if sim.get("mi355", {}).get(key) is not None:
+            from .forward_dynamics import validate as validate_forward_dynamics          # (True / False, or rhs, factor, minv, armature, auto)
+            validate_forward_dynamics(sim["mi355"][key])
     for key in ("force_sensors", "amp_force_sensors"):
         if sim.get("mi355", {}).get(key) is not None:
             from .force_sensors import validate as validate_force_sensors          # (sensors on the foot bodies, cop, corners, auto; plane only)

@@ -146,6 +146,13 @@ class DyrosDynamicWalk(VecTask):
         if spec is not None and spec is not False:
             from .dynamics import Dynamics
             self.dynamics = Dynamics(self, spec)
+        # cfg sim.mi355.forward_dynamics: the solve of M nu_dot = rhs - h, the factor M = L' D L and M^-1, one launch per call
+        # (isaacgymdyros_amd/forward_dynamics.py); off: None, no buffer, and step() makes no extra launch
+        self.forward_dynamics = None
+        spec = self.cfg["sim"].get("mi355", {}).get("forward_dynamics")
+        if spec is not None and spec is not False:
+            from .forward_dynamics import ForwardDynamics
+            self.forward_dynamics = ForwardDynamics(self, spec)
 
     # ------------------------------------------------------------------ native handle
     def _make_config(self):
@@ -426,6 +433,8 @@ class DyrosDynamicWalk(VecTask):
             self.jacobians.refresh()
         if self.dynamics is not None and self.dynamics.auto:
             self.dynamics.refresh()
+        if self.forward_dynamics is not None and self.forward_dynamics.auto:
+            self.forward_dynamics.refresh()
         if self.run_trace is not None:
             self.run_trace.record()
         if self.gait_profile is not None:
@@ -452,6 +461,8 @@ class DyrosDynamicWalk(VecTask):
             self.jacobians.refresh()
         if self.dynamics is not None and self.dynamics.auto:
             self.dynamics.refresh()
+        if self.forward_dynamics is not None and self.forward_dynamics.auto:
+            self.forward_dynamics.refresh()
         # (reset_idx does not touch the observations: the reference recomputes them in the next step's post-physics, :655-669)
 
     def reset(self):
@@ -464,6 +475,8 @@ class DyrosDynamicWalk(VecTask):
             self.jacobians.refresh()
         if self.dynamics is not None and self.dynamics.auto:
             self.dynamics.refresh()
+        if self.forward_dynamics is not None and self.forward_dynamics.auto:
+            self.forward_dynamics.refresh()
         return d
 
     def refresh_rigid_body_state_tensor(self):

@@ -1,0 +1,154 @@
+"""The forward dynamics (include/dyros_forward_dynamics.h, csrc/dw_forward_dynamics.hip): the equation of motion
+M(q) nu_dot + h(q, nu) = [0; tau_joint] + sum J' f_ext  solved for nu_dot on the GPU, in the coordinates of isaacgymdyros_amd/jacobians.py.
+One launch forms M, factors it as L' D L on the sparsity pattern of the kinematic tree and solves; the factor and M^-1 come from the same launch.
+
+Opt-in: cfg["sim"]["mi355"]["forward_dynamics"] = True, or {"rhs": 1, "factor": False, "minv": False, "armature": True, "auto": False}, gives a
+DyrosDynamicWalk env a `forward_dynamics` attribute (None otherwise; TocabiAMPLower: key `amp_forward_dynamics`).  Each call only reads the
+env's buffers, takes no argument that changes from call to call, allocates nothing and does not synchronise, so it sits inside a captured
+rollout step.
+
+The generalised velocity is nu = [root_states[:, 7:10], root_states[:, 10:13], dof_vel], 39 numbers in world axes; DoF j is word 6 + j.  nu_dot
+is its component-wise time derivative.
+
+    solve(rhs=None)                                  copies rhs [N, R, 39] (or [N, 39] when R = 1) into `rhs` when given, one launch, returns
+                                                     `x` [N, R, 39] = M^-1 rhs
+    forward_dynamics(tau_joint=None, gen_force=None) returns `accel` [N, 39] = M^-1 ([0; tau_joint] + gen_force - h), tau_joint [N, 33],
+                                                     gen_force [N, 39] (for instance sum J' f_ext).  h comes from a Dynamics launch of its
+                                                     own and enters as the solve's `sub`: two launches in all
+    refresh()                                        one launch; fills `factor` and `minv` (those the spec holds)
+    factor                                           [N, 39, 39]: D on the diagonal, L strictly below it (M = L' D L, L unit lower triangular),
+                                                     +0.0 elsewhere
+    minv                                             [N, 39, 39] M^-1, symmetric bit for bit
+    rhs, x                                           [N, R, 39], allocated once: copy_ into rhs so that the pointer never changes
+    accel                                            [N, 39], the last forward_dynamics()
+    dof_names                                        of the 33 joint words
+
+minv[:, 6:, 6:] is NOT the inverse of jacobians.mm = mass_matrix[:, 6:, 6:]: the base is free, so the joint block of the inverse is the inverse
+of the joint block's Schur complement over the base.  "rhs": R right-hand sides per env, 1 .. 8.  "armature": True factors M with the env's
+dof_armature on the joints' diagonal, as jacobians' mass matrix carries it.  "auto": True calls refresh() after every step(), after reset_idx()
+and reset().
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import cbind
+from . import jacobians as JM
+
+K = cbind.constants("dyros_forward_dynamics.h", "dwl_")
+EXPORTS = list(cbind.signatures("dyros_forward_dynamics.h", "dwl_"))
+NB, NV, PATTERN, GROUP, MAX_RHS, TABLE_WORDS = K["DWL_NUM_BODIES"], K["DWL_NV"], K["DWL_PATTERN"], K["DWL_GROUP"], K["DWL_MAX_RHS"], K["DWL_TABLE_WORDS"]
+DEFAULTS = {"rhs": 1, "factor": False, "minv": False, "armature": True, "auto": False}
+
+
+def declare(lib) -> dict:
+    return cbind.declare(lib, "dyros_forward_dynamics.h", "dwl_")
+
+
+def pack_table(api: dict, model) -> np.ndarray:
+    """The device table's DWL_TABLE_WORDS words as a uint32 array (dwl_pack_table: dwj_pack_table's table, then the pattern's row starts and
+    columns; raises for a model it refuses)."""
+    import ctypes as C
+    m, t = model if isinstance(model, JM.DwjModel) else JM.model_struct(model), np.zeros(TABLE_WORDS, np.uint32)
+    cbind.check(api, api["pack_table"](C.byref(m), t.ctypes.data))
+    return t
+
+
+def resolve(spec) -> dict:
+    """The cfg value as a full dict; None when the feature is off (None or False).  ValueError for anything else that is not True or a dict of
+    the keys of DEFAULTS: rhs an int in 1 .. DWL_MAX_RHS, the others bool."""
+    if spec is None or spec is False:
+        return None
+    if spec is True:
+        spec = {}
+    if not isinstance(spec, dict):
+        raise ValueError("forward_dynamics must be True, False or a dict with %s" % ", ".join(DEFAULTS))
+    unknown = set(spec) - set(DEFAULTS)
+    if unknown:
+        raise ValueError("forward_dynamics: unknown keys %s" % sorted(unknown, key=str))
+    out = dict(DEFAULTS, **spec)
+    for k in ("factor", "minv", "armature", "auto"):
+        if not isinstance(out[k], bool):
+            raise ValueError("forward_dynamics.%s must be True or False" % k)
+    if isinstance(out["rhs"], bool) or not isinstance(out["rhs"], int) or not 1 <= out["rhs"] <= MAX_RHS:
+        raise ValueError("forward_dynamics.rhs must be an integer in 1..%d" % MAX_RHS)
+    return out
+
+
+def validate(spec) -> None:
+    """Checks of cfg sim.mi355.forward_dynamics (config.validate_cfg)."""
+    resolve(spec)
+
+
+class ForwardDynamics:
+    """The solve, the factor and the inverse of the mass matrix of one env object's bound buffers (see the module docstring).  host: a
+    DyrosDynamicWalk (TocabiAMPLower hands its physics host); vel_at_com: the host's root_vel_at_com unless given.  Buffers are allocated here,
+    once."""
+
+    def __init__(self, host, spec=True, vel_at_com=None):
+        import torch
+        from . import _lib
+        from .dynamics import Dynamics
+        from .ppo_update import _req
+        model = host.model
+        spec = resolve(spec)
+        if spec is None:
+            raise ValueError("ForwardDynamics: the spec switches the feature off")
+        self.api = declare(_lib.load()[0])
+        self.host = host
+        N, dev, R = host.num_envs, host._tdev, spec["rhs"]
+        self._tdev = dev
+        self.num_envs, self.auto, self.nrhs = N, spec["auto"], R
+        self.dof_names = list(model.dof_names)
+        self.vel_at_com = int(bool(host._ccfg.root_vel_at_com if vel_at_com is None else vel_at_com))
+        self.table = torch.from_numpy(pack_table(self.api, model).view(np.int32)).to(dev)
+        f = dict(dtype=torch.float32, device=dev)
+        self.rhs = torch.zeros(N, R, NV, **f)
+        self.x = torch.zeros(N, R, NV, **f)
+        self.factor = torch.zeros(N, NV, NV, **f) if spec["factor"] else None
+        self.minv = torch.zeros(N, NV, NV, **f) if spec["minv"] else None
+        # forward_dynamics(): a right-hand side and a solution of its own, and h from a Dynamics of its own (bias alone, one launch)
+        self._fd_rhs = torch.zeros(N, 1, NV, **f)
+        self.accel = torch.zeros(N, NV, **f)
+        self._bias = Dynamics(host, {"bias": True, "gravity": False}, vel_at_com=self.vel_at_com)
+        # the entry point's arguments, checked once: no argument changes from call to call (the host's buffers are bound once)
+        b = host._buf
+        p = lambda name, dt, **kw: _req(name, b[name], dt, **kw).data_ptr()          # noqa: E731
+        ptr = lambda t: None if t is None else t.data_ptr()          # noqa: E731
+        common = (N, self.table.data_ptr(), p("root_states", torch.float32, shape=(N, 13)), p("dof_state", torch.float32, numel=N * 66),
+                  p("mass_scale", torch.float32, shape=(N, NB)), p("dof_armature", torch.float32, shape=(N, K["DWL_NUM_DOF"])) if spec["armature"] else None,
+                  self.vel_at_com)
+        self._solve_args = common + (self.rhs.data_ptr(), R, None, self.x.data_ptr(), None, None)
+        self._fd_args = common + (self._fd_rhs.data_ptr(), 1, self._bias.bias.data_ptr(), self.accel.data_ptr(), None, None)
+        any_refresh = self.factor is not None or self.minv is not None
+        self._refresh_args = common + (None, 0, None, None, ptr(self.factor), ptr(self.minv)) if any_refresh else None
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self._tdev).cuda_stream
+
+    def refresh(self):
+        """One launch on torch's current stream: `factor` and `minv`, those the spec holds (none: no launch)."""
+        if self._refresh_args is not None:
+            cbind.check(self.api, self.api["solve"](*self._refresh_args, self._stream()))
+
+    def solve(self, rhs=None):
+        """x = M^-1 rhs: copies rhs [N, R, 39] (R = 1: [N, 39] too) into `rhs` when given, one launch on torch's current stream; returns `x`."""
+        if rhs is not None:
+            self.rhs.copy_(rhs.reshape(self.rhs.shape))
+        cbind.check(self.api, self.api["solve"](*self._solve_args, self._stream()))
+        return self.x
+
+    def forward_dynamics(self, tau_joint=None, gen_force=None):
+        """accel = M^-1 ([0; tau_joint] + gen_force - h): tau_joint [N, 33] and gen_force [N, 39], each or None (zero).  Two launches on torch's
+        current stream, the bias forces and the solve; returns `accel` [N, 39]."""
+        r = self._fd_rhs[:, 0]
+        if gen_force is not None:
+            r.copy_(gen_force)
+        else:
+            r.zero_()
+        if tau_joint is not None:
+            r[:, 6:] += tau_joint
+        self._bias.refresh()
+        cbind.check(self.api, self.api["solve"](*self._fd_args, self._stream()))
+        return self.accel
