@@ -34,7 +34,10 @@ both feet; rows linear then angular, columns the root's linear and angular veloc
 com_jacobian [T, 3, 39].  With --dynamics-forces it also turns the bias-force, gravity and momentum tensors on (isaacgymdyros_amd/dynamics.py,
 DESIGN.md section 24) and adds bias [T, 39], gravity [T, 39] and momentum [T, 6] to each file; without the flag the files are unchanged.  With --dynamics-accel it
 turns the forward dynamics on (isaacgymdyros_amd/forward_dynamics.py) and adds minv [T, 39, 39] = M^-1 and
-accel_zero_torque [T, 39] = M^-1 (-h), the acceleration of the unactuated robot in free flight; without the flag the files are unchanged.
+accel_zero_torque [T, 39] = M^-1 (-h), the acceleration of the unactuated robot in free flight; without the flag the files are unchanged.  With --dynamics-contact it turns the
+contact-consistent dynamics on (isaacgymdyros_amd/contact_dynamics.py) with both feet planted and adds contact_jacobian
+[T, 12, 39], contact_lambda [T, 12, 12] (the contact-space inertia) and contact_force_zero_torque [T, 2, 6], the ground reaction (force, then
+moment about the sensor frame's origin, world axes) the unactuated robot with planted feet would get; without the flag the files are unchanged.
 """
 from __future__ import annotations
 
@@ -93,6 +96,8 @@ def run(args):
             cfg["sim"]["mi355"]["dynamics"] = {"momentum": True, "auto": True}
         if args.dynamics_accel:
             cfg["sim"]["mi355"]["forward_dynamics"] = {"minv": True, "auto": True}
+        if args.dynamics_contact:
+            cfg["sim"]["mi355"]["contact_dynamics"] = {"auto": True}
         os.makedirs(args.dynamics_dir, exist_ok=True)
     env = DyrosDynamicWalk(cfg, args.device, 0, True)
     traces_written = 0
@@ -119,6 +124,11 @@ def run(args):
     if accel:
         rec_minv = torch.zeros(args.max_steps, dynamics_k, 39, 39, device=dev)
         rec_acc = torch.zeros(args.max_steps, dynamics_k, 39, device=dev)
+    contact = bool(dynamics_k and args.dynamics_contact)
+    if contact:
+        rec_cjac = torch.zeros(args.max_steps, dynamics_k, 12, 39, device=dev)
+        rec_clam = torch.zeros(args.max_steps, dynamics_k, 12, 12, device=dev)
+        rec_cf = torch.zeros(args.max_steps, dynamics_k, 2, 6, device=dev)
     played = 0
     ck = PK.load(args.checkpoint)
     n_obs, n_act = int(ck["model"][PK.PREFIX + "actor_mlp.0.weight"].shape[1]), int(ck["model"][PK.PREFIX + "mu.weight"].shape[0])
@@ -154,6 +164,11 @@ def run(args):
         if accel:
             rec_minv[_n].copy_(env.forward_dynamics.minv[:dynamics_k])
             rec_acc[_n].copy_(env.forward_dynamics.forward_dynamics()[:dynamics_k])
+        if contact:
+            env.contact_dynamics.forward_dynamics()
+            rec_cjac[_n].copy_(env.contact_dynamics.jc[:dynamics_k])
+            rec_clam[_n].copy_(env.contact_dynamics.lambda_[:dynamics_k])
+            rec_cf[_n].copy_(env.contact_dynamics.force[:dynamics_k])
         played = _n + 1
         cr += r.view(N)
         steps += 1
@@ -211,6 +226,9 @@ def run(args):
                 more = dict(bias=rec_bias[:played, e].cpu().numpy(), gravity=rec_grav[:played, e].cpu().numpy(), momentum=rec_mom[:played, e].cpu().numpy())
             if accel:
                 more.update(minv=rec_minv[:played, e].cpu().numpy(), accel_zero_torque=rec_acc[:played, e].cpu().numpy())
+            if contact:
+                more.update(contact_jacobian=rec_cjac[:played, e].cpu().numpy(), contact_lambda=rec_clam[:played, e].cpu().numpy(),
+                            contact_force_zero_torque=rec_cf[:played, e].cpu().numpy())
             np.savez(os.path.join(args.dynamics_dir, "dynamics_env%d.npz" % e), names=np.asarray(jc.names), dof_names=np.asarray(jc.dof_names),
                      dt=np.float64(jc.dt), jacobian=rec_jac[:played, e].cpu().numpy(), mass_matrix=rec_mm[:played, e].cpu().numpy(),
                      com_jacobian=rec_cj[:played, e].cpu().numpy(), **more)
@@ -251,6 +269,7 @@ def main():
     ap.add_argument("--dynamics-dir", default=None, help="turn the Jacobian and mass-matrix tensors on and write dynamics_env<id>.npz (head and foot Jacobians, M, COM Jacobian) here")
     ap.add_argument("--dynamics-envs", type=int, default=1, help="record envs 0 .. K-1")
     ap.add_argument("--dynamics-accel", action="store_true", help="with --dynamics-dir: add the inverse of the mass matrix and the zero-torque acceleration M^-1 (-h) to each file")
+    ap.add_argument("--dynamics-contact", action="store_true", help="with --dynamics-dir: add the feet's contact Jacobian, the contact-space inertia and the zero-torque ground reaction with planted feet to each file")
     ap.add_argument("--dynamics-forces", action="store_true", help="with --dynamics-dir: add the bias forces, the gravity forces and the momentum to each file")
     ap.add_argument("--device", default="cuda:0")
     run(ap.parse_args())

@@ -125,6 +125,10 @@ def validate_cfg(cfg: dict) -> None:
         if sim.get("mi355", {}).get(key) is not None:
             from .forward_dynamics import validate as validate_forward_dynamics          # (True / False, or rhs, factor, minv, armature, auto)
             validate_forward_dynamics(sim["mi355"][key])
+    for key in ("contact_dynamics", "amp_contact_dynamics"):
+        if sim.get("mi355", {}).get(key) is not None:
+            from .contact_dynamics import validate as validate_contact_dynamics          # (True / False, or contacts, rhs, jacobian, lambda, lambda_inv, minv_jt, armature, auto)
+            validate_contact_dynamics(sim["mi355"][key])
     for key in ("force_sensors", "amp_force_sensors"):
         if sim.get("mi355", {}).get(key) is not None:
             from .force_sensors import validate as validate_force_sensors          # (sensors on the foot bodies, cop, corners, auto; plane only)

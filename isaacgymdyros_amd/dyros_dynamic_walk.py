@@ -153,6 +153,14 @@ class DyrosDynamicWalk(VecTask):
         if spec is not None and spec is not False:
             from .forward_dynamics import ForwardDynamics
             self.forward_dynamics = ForwardDynamics(self, spec)
+        # cfg sim.mi355.contact_dynamics: the equation of motion under rigid contact constraints: J_c, the contact-space inertia, and the
+        # acceleration and ground reaction a torque causes while the feet stay planted, one launch per call
+        # (isaacgymdyros_amd/contact_dynamics.py); off: None, no buffer, and step() makes no extra launch
+        self.contact_dynamics = None
+        spec = self.cfg["sim"].get("mi355", {}).get("contact_dynamics")
+        if spec is not None and spec is not False:
+            from .contact_dynamics import ContactDynamics
+            self.contact_dynamics = ContactDynamics(self, spec)
 
     # ------------------------------------------------------------------ native handle
     def _make_config(self):
@@ -435,6 +443,8 @@ class DyrosDynamicWalk(VecTask):
             self.dynamics.refresh()
         if self.forward_dynamics is not None and self.forward_dynamics.auto:
             self.forward_dynamics.refresh()
+        if self.contact_dynamics is not None and self.contact_dynamics.auto:
+            self.contact_dynamics.refresh()
         if self.run_trace is not None:
             self.run_trace.record()
         if self.gait_profile is not None:
@@ -463,6 +473,8 @@ class DyrosDynamicWalk(VecTask):
             self.dynamics.refresh()
         if self.forward_dynamics is not None and self.forward_dynamics.auto:
             self.forward_dynamics.refresh()
+        if self.contact_dynamics is not None and self.contact_dynamics.auto:
+            self.contact_dynamics.refresh()
         # (reset_idx does not touch the observations: the reference recomputes them in the next step's post-physics, :655-669)
 
     def reset(self):
@@ -477,6 +489,8 @@ class DyrosDynamicWalk(VecTask):
             self.dynamics.refresh()
         if self.forward_dynamics is not None and self.forward_dynamics.auto:
             self.forward_dynamics.refresh()
+        if self.contact_dynamics is not None and self.contact_dynamics.auto:
+            self.contact_dynamics.refresh()
         return d
 
     def refresh_rigid_body_state_tensor(self):

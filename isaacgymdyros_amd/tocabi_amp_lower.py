@@ -200,6 +200,11 @@ class TocabiAMPLower(VecTask):
         self._amp_forward_dynamics_spec = cfg["sim"].get("mi355", {}).get("amp_forward_dynamics")
         from .forward_dynamics import validate as validate_forward_dynamics
         validate_forward_dynamics(self._amp_forward_dynamics_spec)
+        # cfg sim.mi355.amp_contact_dynamics: the contact-consistent dynamics over the physics host's bound buffers
+        # (isaacgymdyros_amd/contact_dynamics.py); off: None.  This class' own key for the same reason
+        self._amp_contact_dynamics_spec = cfg["sim"].get("mi355", {}).get("amp_contact_dynamics")
+        from .contact_dynamics import validate as validate_contact_dynamics
+        validate_contact_dynamics(self._amp_contact_dynamics_spec)
         e["numObservations"] = (NUM_OBS + NUM_ACTIONS) * self.num_obs_his - NUM_ACTIONS            # :83
         e["numActions"] = NUM_ACTIONS
         super().__init__(config=cfg, sim_device=sim_device, graphics_device_id=graphics_device_id, headless=headless)
@@ -210,7 +215,7 @@ class TocabiAMPLower(VecTask):
         pc["sim"].update({k: copy.deepcopy(v) for k, v in cfg["sim"].items() if k != "mi355"})
         # (physx.num_position_iterations + num_velocity_iterations = the contact solver's iteration count, as the task yaml gives them:
         #  4 + 0 for this task, cfg/task/TocabiAMPLower.yaml)
-        pc["sim"]["mi355"].update({k: v for k, v in cfg["sim"].get("mi355", {}).items() if k not in ("amp_episode_stats", "amp_body_states", "amp_force_sensors", "amp_jacobians", "amp_dynamics", "amp_forward_dynamics")})
+        pc["sim"]["mi355"].update({k: v for k, v in cfg["sim"].get("mi355", {}).items() if k not in ("amp_episode_stats", "amp_body_states", "amp_force_sensors", "amp_jacobians", "amp_dynamics", "amp_forward_dynamics", "amp_contact_dynamics")})
         pc["env"]["perturbation"] = False
         # spawn height: the reference's 0.89 (:394) puts the soles 2.2 cm INTO the plane in the initial pose; PhysX resolves that
         # positionally, this simulator's contact model through a velocity bias (erp), which launches the robot at 2 m/s.  Default
@@ -399,6 +404,10 @@ class TocabiAMPLower(VecTask):
         if self._amp_forward_dynamics_spec is not None and self._amp_forward_dynamics_spec is not False:
             from .forward_dynamics import ForwardDynamics
             self.forward_dynamics = ForwardDynamics(self._phys, self._amp_forward_dynamics_spec)
+        self.contact_dynamics = None
+        if self._amp_contact_dynamics_spec is not None and self._amp_contact_dynamics_spec is not False:
+            from .contact_dynamics import ContactDynamics
+            self.contact_dynamics = ContactDynamics(self._phys, self._amp_contact_dynamics_spec)
 
     # ------------------------------------------------------------------ helpers
     def _rand(self, *shape):
@@ -1000,6 +1009,8 @@ class TocabiAMPLower(VecTask):
             self.dynamics.refresh()
         if self.forward_dynamics is not None and self.forward_dynamics.auto:
             self.forward_dynamics.refresh()
+        if self.contact_dynamics is not None and self.contact_dynamics.auto:
+            self.contact_dynamics.refresh()
         return out
 
     def refresh_jacobian_tensors(self):
