@@ -24,6 +24,7 @@ import ctypes as C
 import numpy as np
 
 from . import cbind
+from .model_tensors import ModelTensor, ptr, resolve_front
 
 K = cbind.constants("dyros_bodies.h", "dwb_")
 EXPORTS = list(cbind.signatures("dyros_bodies.h", "dwb_"))
@@ -83,19 +84,9 @@ def body_ids(bodies, names) -> list:
 def resolve(spec, names=None) -> dict:
     """The cfg value as a full dict; None when the tensor is off (None or False).  ValueError for anything else that is not True or a dict of
     bodies / com / auto.  names: the model's body names (None: the packaged model's)."""
-    if spec is None or spec is False:
+    out = resolve_front("body_states", spec, DEFAULTS, ("com", "auto"), "bodies, com and auto")
+    if out is None:
         return None
-    if spec is True:
-        spec = {}
-    if not isinstance(spec, dict):
-        raise ValueError("body_states must be True, False or a dict with bodies, com and auto")
-    unknown = set(spec) - set(DEFAULTS)
-    if unknown:
-        raise ValueError("body_states: unknown keys %s" % sorted(unknown))
-    out = dict(DEFAULTS, **spec)
-    for k in ("com", "auto"):
-        if not isinstance(out[k], bool):
-            raise ValueError("body_states.%s must be True or False" % k)
     if names is None:
         from .model import load_model
         names = load_model().body_names
@@ -116,47 +107,36 @@ def select_parents(ids, body_parent) -> list:
     return [first.get(body_parent[g], -1) if body_parent[g] >= 0 else -1 for g in ids]
 
 
-class BodyStates:
+class BodyStates(ModelTensor):
     """The rigid-body states of one env object's bound buffers (see the module docstring).  host: a DyrosDynamicWalk (TocabiAMPLower hands its
     physics host); vel_at_com: the host's root_vel_at_com unless given.  Buffers are allocated here, once."""
 
+    WHAT = "tensor"
+
     def __init__(self, host, spec=True, vel_at_com=None):
-        import torch
-        from . import _lib
-        from .ppo_update import _req
         model = host.model
         spec = resolve(spec, model.body_names)
-        if spec is None:
-            raise ValueError("BodyStates: the spec switches the tensor off")
-        self.api = declare(_lib.load()[0])
-        self.host = host
-        N, dev = host.num_envs, host._tdev
-        self._tdev = dev
-        self.num_envs, self.auto = N, spec["auto"]
+        super().__init__(host, spec, declare)
+        N = self.num_envs
         self.ids = spec["ids"]
         self.names = [model.body_names[g] for g in self.ids]
         self.parents = select_parents(self.ids, model.body_parent)
-        self.vel_at_com = int(bool(host._ccfg.root_vel_at_com if vel_at_com is None else vel_at_com))
+        self.vel_at_com = self._vel_at_com(vel_at_com)
         self.dt = float(host.dt) * int(getattr(host, "skipframe", 1))
-        self.table = torch.from_numpy(pack_table(self.api, model).view(np.int32)).to(dev)
+        self.table = self._upload(pack_table(self.api, model))
         nb = len(self.ids)
-        self.states = torch.zeros(N, nb, ROW, dtype=torch.float32, device=dev)
+        self.states = self._zeros(N, nb, ROW)
         self.pos, self.rot = self.states[..., 0:3], self.states[..., 3:7]
         self.vel, self.ang_vel = self.states[..., 7:10], self.states[..., 10:13]
-        self.com = torch.zeros(N, K["DWB_COM_WORDS"], dtype=torch.float32, device=dev) if spec["com"] else None
+        self.com = self._zeros(N, K["DWB_COM_WORDS"]) if spec["com"] else None
         whole = self.ids == list(range(NB))
         self._ids_c = None if whole else (C.c_int32 * nb)(*self.ids)
-        # dwb_refresh's arguments, checked once: no argument changes from call to call (the host's buffers are bound once)
-        b = host._buf
-        p = lambda name, dt, **kw: _req(name, b[name], dt, **kw).data_ptr()          # noqa: E731
-        self._args = (N, self.table.data_ptr(), p("root_states", torch.float32, shape=(N, 13)), p("dof_state", torch.float32, numel=N * 66),
-                      p("mass_scale", torch.float32, shape=(N, NB)), self._ids_c, 0 if whole else nb, self.vel_at_com, self.states.data_ptr(),
-                      None if self.com is None else self.com.data_ptr())
+        self._args = self._inputs() + (self._in("mass_scale", shape=(N, NB)), self._ids_c, 0 if whole else nb, self.vel_at_com,
+                                       self.states.data_ptr(), ptr(self.com))
 
     def refresh(self):
         """One launch on torch's current stream; returns `states`."""
-        import torch
-        cbind.check(self.api, self.api["refresh"](*self._args, torch.cuda.current_stream(self._tdev).cuda_stream))
+        self._launch("refresh", self._args)
         return self.states
 
     def index(self, name: str) -> int:

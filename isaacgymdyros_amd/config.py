@@ -5,6 +5,8 @@ from __future__ import annotations
 
 import copy
 
+from . import model_tensors
+
 
 def default_cfg(num_envs: int = 4096, sim_device: str = "cuda:0") -> dict:
     return {
@@ -110,29 +112,8 @@ def validate_cfg(cfg: dict) -> None:
     if sim.get("mi355", {}).get("gait_profile") is not None:
         from .gait_profile import validate as validate_gait_profile          # (bins one of 12, 24, 36, 72, 144; the two filters)
         validate_gait_profile(sim["mi355"]["gait_profile"])
-    if sim.get("mi355", {}).get("body_states") is not None:
-        from .body_states import validate as validate_body_states          # (True / False, or bodies by name or Gym id, com, auto)
-        validate_body_states(sim["mi355"]["body_states"])
-    for key in ("jacobians", "amp_jacobians"):
-        if sim.get("mi355", {}).get(key) is not None:
-            from .jacobians import validate as validate_jacobians          # (True / False, or bodies, jacobian, mass_matrix, com_jacobian, armature, auto)
-            validate_jacobians(sim["mi355"][key])
-    for key in ("dynamics", "amp_dynamics"):
-        if sim.get("mi355", {}).get(key) is not None:
-            from .dynamics import validate as validate_dynamics          # (True / False, or bias, gravity, inverse_dynamics, momentum, armature, auto)
-            validate_dynamics(sim["mi355"][key])
-    for key in ("forward_dynamics", "amp_forward_dynamics"):
-        if sim.get("mi355", {}).get(key) is not None:
-            from .forward_dynamics import validate as validate_forward_dynamics          # (True / False, or rhs, factor, minv, armature, auto)
-            validate_forward_dynamics(sim["mi355"][key])
-    for key in ("contact_dynamics", "amp_contact_dynamics"):
-        if sim.get("mi355", {}).get(key) is not None:
-            from .contact_dynamics import validate as validate_contact_dynamics          # (True / False, or contacts, rhs, jacobian, lambda, lambda_inv, minv_jt, armature, auto)
-            validate_contact_dynamics(sim["mi355"][key])
-    for key in ("force_sensors", "amp_force_sensors"):
-        if sim.get("mi355", {}).get(key) is not None:
-            from .force_sensors import validate as validate_force_sensors          # (sensors on the foot bodies, cop, corners, auto; plane only)
-            validate_force_sensors(sim["mi355"][key], cfg.get("terrain"))
+    for prefix in ("", "amp_"):          # (the model tensors: isaacgymdyros_amd/model_tensors.py's table; amp_: TocabiAMPLower's keys)
+        model_tensors.validate_all(cfg, prefix)
     iters = int(px.get("num_position_iterations", 4)) + int(px.get("num_velocity_iterations", 1))
     if not 1 <= iters <= 64:
         raise ValueError("physx.num_position_iterations + num_velocity_iterations must be in 1..64")

@@ -41,6 +41,7 @@ import numpy as np
 
 from . import cbind
 from . import jacobians as JM
+from .model_tensors import ModelTensor, joint_space_force, ptr, resolve_front
 
 K = cbind.constants("dyros_contact_dynamics.h", "dwc_")
 EXPORTS = list(cbind.signatures("dyros_contact_dynamics.h", "dwc_"))
@@ -80,19 +81,9 @@ def resolve(spec, names=None, carriers=None) -> dict:
     """The cfg value as a full dict, plus "ids" and "pos" of the contacts; None when the feature is off (None or False).  ValueError for
     anything else that is not True or a dict of the keys of DEFAULTS.  names, carriers: the model's body names and body_moving (None: the
     packaged model's)."""
-    if spec is None or spec is False:
+    out = resolve_front("contact_dynamics", spec, DEFAULTS, ("jacobian", "lambda", "lambda_inv", "minv_jt", "armature", "auto"))
+    if out is None:
         return None
-    if spec is True:
-        spec = {}
-    if not isinstance(spec, dict):
-        raise ValueError("contact_dynamics must be True, False or a dict with %s" % ", ".join(DEFAULTS))
-    unknown = set(spec) - set(DEFAULTS)
-    if unknown:
-        raise ValueError("contact_dynamics: unknown keys %s" % sorted(unknown, key=str))
-    out = dict(DEFAULTS, **spec)
-    for k in ("jacobian", "lambda", "lambda_inv", "minv_jt", "armature", "auto"):
-        if not isinstance(out[k], bool):
-            raise ValueError("contact_dynamics.%s must be True or False" % k)
     if isinstance(out["rhs"], bool) or not isinstance(out["rhs"], int) or not 1 <= out["rhs"] <= MAX_RHS:
         raise ValueError("contact_dynamics.rhs must be an integer in 1..%d" % MAX_RHS)
     if names is None or carriers is None:
@@ -133,65 +124,49 @@ def validate(spec) -> None:
     resolve(spec)
 
 
-class ContactDynamics:
+class ContactDynamics(ModelTensor):
     """The contact Jacobian, the contact-space inertia and the constrained forward dynamics of one env object's bound buffers (see the module
     docstring).  host: a DyrosDynamicWalk (TocabiAMPLower hands its physics host); vel_at_com: the host's root_vel_at_com unless given.
     Buffers are allocated here, once."""
 
+    WHAT = "feature"
+
     def __init__(self, host, spec=True, vel_at_com=None):
-        import torch
-        from . import _lib
         from .dynamics import Dynamics
-        from .ppo_update import _req
         model = host.model
         spec = resolve(spec, model.body_names, model.body_moving)
-        if spec is None:
-            raise ValueError("ContactDynamics: the spec switches the feature off")
-        self.api = declare(_lib.load()[0])
-        self.host = host
-        N, dev, R = host.num_envs, host._tdev, spec["rhs"]
-        self._tdev = dev
-        self.num_envs, self.auto, self.nrhs = N, spec["auto"], R
+        super().__init__(host, spec, declare)
+        N, R = self.num_envs, spec["rhs"]
+        self.nrhs = R
         self.ids, self.pos = list(spec["ids"]), [list(p) for p in spec["pos"]]
         self.names = [model.body_names[g] for g in self.ids]
         self.num_contacts = len(self.ids)
         m = self.rows = 6 * self.num_contacts
         self.dof_names = list(model.dof_names)
-        self.vel_at_com = int(bool(host._ccfg.root_vel_at_com if vel_at_com is None else vel_at_com))
-        self.table = torch.from_numpy(pack_table(self.api, model, self.ids, self.pos).view(np.int32)).to(dev)
-        f = dict(dtype=torch.float32, device=dev)
-        self.jc = torch.zeros(N, m, NV, **f) if spec["jacobian"] else None
-        self.jdnu = torch.zeros(N, m, **f) if spec["jacobian"] else None
-        self.lambda_ = torch.zeros(N, m, m, **f) if spec["lambda"] else None
-        self.lambda_inv = torch.zeros(N, m, m, **f) if spec["lambda_inv"] else None
-        self.minv_jt = torch.zeros(N, m, NV, **f) if spec["minv_jt"] else None
-        self.rhs = torch.zeros(N, R, NV, **f)
-        self.gamma = torch.zeros(N, m, **f)
-        self.accel_all = torch.zeros(N, R, NV, **f)
-        self.force_all = torch.zeros(N, R, m, **f)
+        self.vel_at_com = self._vel_at_com(vel_at_com)
+        self.table = self._upload(pack_table(self.api, model, self.ids, self.pos))
+        self.jc = self._zeros(N, m, NV) if spec["jacobian"] else None
+        self.jdnu = self._zeros(N, m) if spec["jacobian"] else None
+        self.lambda_ = self._zeros(N, m, m) if spec["lambda"] else None
+        self.lambda_inv = self._zeros(N, m, m) if spec["lambda_inv"] else None
+        self.minv_jt = self._zeros(N, m, NV) if spec["minv_jt"] else None
+        self.rhs = self._zeros(N, R, NV)
+        self.gamma = self._zeros(N, m)
+        self.accel_all = self._zeros(N, R, NV)
+        self.force_all = self._zeros(N, R, m)
         # forward_dynamics(): a right-hand side, a gamma and solutions of its own, and h from a Dynamics of its own (bias alone, one launch)
-        self._fd_rhs = torch.zeros(N, 1, NV, **f)
-        self._fd_gamma = torch.zeros(N, m, **f)
-        self.accel = torch.zeros(N, NV, **f)
-        self.force = torch.zeros(N, self.num_contacts, 6, **f)
+        self._fd_rhs = self._zeros(N, 1, NV)
+        self._fd_gamma = self._zeros(N, m)
+        self.accel = self._zeros(N, NV)
+        self.force = self._zeros(N, self.num_contacts, 6)
         self._bias = Dynamics(host, {"bias": True, "gravity": False}, vel_at_com=self.vel_at_com)
-        # the entry point's arguments, checked once: no argument changes from call to call (the host's buffers are bound once)
-        b = host._buf
-        p = lambda name, dt, **kw: _req(name, b[name], dt, **kw).data_ptr()          # noqa: E731
-        ptr = lambda t: None if t is None else t.data_ptr()          # noqa: E731
-        common = (N, self.table.data_ptr(), p("root_states", torch.float32, shape=(N, 13)), p("dof_state", torch.float32, numel=N * 66),
-                  p("mass_scale", torch.float32, shape=(N, NB)), p("dof_armature", torch.float32, shape=(N, K["DWC_NUM_DOF"])) if spec["armature"] else None,
-                  self.vel_at_com)
+        common = self._inputs(spec["armature"]) + (self.vel_at_com,)
         none5 = (None,) * 5
         self._solve_args = common + (self.rhs.data_ptr(), R, None, self.gamma.data_ptr()) + none5 + (self.accel_all.data_ptr(), self.force_all.data_ptr())
         self._fd_args = common + (self._fd_rhs.data_ptr(), 1, self._bias.bias.data_ptr(), self._fd_gamma.data_ptr()) + none5 + (self.accel.data_ptr(),
                                                                                                                                   self.force.data_ptr())
         outs = (ptr(self.jc), ptr(self.jdnu), ptr(self.minv_jt), ptr(self.lambda_inv), ptr(self.lambda_))
         self._refresh_args = common + (None, 0, None, None) + outs + (None, None) if any(o is not None for o in outs) else None
-
-    def _stream(self):
-        import torch
-        return torch.cuda.current_stream(self._tdev).cuda_stream
 
     def index(self, name: str) -> int:
         """The contact (0 .. K - 1) on the body named."""
@@ -202,31 +177,25 @@ class ContactDynamics:
     def refresh(self):
         """One launch on torch's current stream: `jc`, `jdnu`, `lambda_`, `lambda_inv` and `minv_jt`, those the spec holds (none: no launch)."""
         if self._refresh_args is not None:
-            cbind.check(self.api, self.api["solve"](*self._refresh_args, self._stream()))
+            self._launch("solve", self._refresh_args)
 
     def solve(self, rhs=None):
         """The constrained solve of b = rhs with `gamma`: copies rhs [N, R, 39] (R = 1: [N, 39] too) into `rhs` when given, one launch on torch's
         current stream; returns `accel_all` [N, R, 39] and leaves `force_all` [N, R, m]."""
         if rhs is not None:
             self.rhs.copy_(rhs.reshape(self.rhs.shape))
-        cbind.check(self.api, self.api["solve"](*self._solve_args, self._stream()))
+        self._launch("solve", self._solve_args)
         return self.accel_all
 
     def forward_dynamics(self, tau_joint=None, gen_force=None, contact_accel=None):
         """accel = the nu_dot of b = [0; tau_joint] + gen_force - h under the contacts, which accelerate by contact_accel [N, m] (None: zero):
         tau_joint [N, 33] and gen_force [N, 39], each or None (zero).  Two launches on torch's current stream, the bias forces and the solve;
         returns `accel` [N, 39] and leaves the ground reaction in `force` [N, K, 6]."""
-        r = self._fd_rhs[:, 0]
-        if gen_force is not None:
-            r.copy_(gen_force)
-        else:
-            r.zero_()
-        if tau_joint is not None:
-            r[:, 6:] += tau_joint
+        joint_space_force(self._fd_rhs[:, 0], tau_joint, gen_force)
         if contact_accel is not None:
             self._fd_gamma.copy_(contact_accel.reshape(self._fd_gamma.shape))
         else:
             self._fd_gamma.zero_()
         self._bias.refresh()
-        cbind.check(self.api, self.api["solve"](*self._fd_args, self._stream()))
+        self._launch("solve", self._fd_args)
         return self.accel

@@ -12,16 +12,14 @@
 #include <stdio.h>
 
 #include "dw_bodies.h"
+#include "dw_group.h"
 
 namespace {
 
-char s_err[256] = "";
-int fail(const char *msg) { snprintf(s_err, sizeof(s_err), "%s", msg); return -1; }
-int fail_hip(const char *who, hipError_t e) { snprintf(s_err, sizeof(s_err), "%s: %s", who, hipGetErrorString(e)); return -1; }
+dwg::Err s_err;
 
 constexpr int G = DWB_GROUP, TPB = DWB_GROUP * DWB_LANES;
 static_assert(TPB % 64 == 0 && DWB_LANES == 16 && DWB_MAX_LEAVES <= DWB_LANES, "whole waves, sixteen lanes per env, room for a lane per path");
-static_assert(DWB_TABLE_WORDS % 4 == 0, "the table is loaded in 16-byte pieces");
 static_assert((G * dwb::IN_ROOT) % 4 == 0 && (G * DWB_ROW) % 4 == 0, "a group's blocks start on 16 bytes");
 static_assert((DWB_TABLE_WORDS + G * (dwb::IN_ROOT + dwb::IN_DOF + dwb::NB + dwb::MVW + DWB_COM_WORDS) + dwb::NB) * 4 <= 64 * 1024, "static LDS");
 
@@ -42,17 +40,10 @@ __global__ __launch_bounds__(TPB) void dwb_k_refresh(int n, const uint4 *__restr
     const int t = threadIdx.x, e0 = blockIdx.x * G;
     const int ne = n - e0 < G ? n - e0 : G;          // envs of this workgroup (the last one may hold fewer)
     // ---- loads: consecutive lanes, consecutive words ----
-    for (int i = t; i < DWB_TABLE_WORDS / 4; i += TPB) s_tab4[i] = table[i];
-    {
-        const float *src = root_states + (size_t)e0 * dwb::IN_ROOT;
-        for (int i = t; i < ne * dwb::IN_ROOT; i += TPB) s_root[i] = src[i];
-        src = dof_state + (size_t)e0 * dwb::IN_DOF;
-        for (int i = t; i < ne * dwb::IN_DOF; i += TPB) s_dof[i] = src[i];
-        if (mass_scale != nullptr && com != nullptr) {
-            src = mass_scale + (size_t)e0 * dwb::NB;
-            for (int i = t; i < ne * dwb::NB; i += TPB) s_ms[i] = src[i];
-        }
-    }
+    dwg::load_table<TPB, DWB_TABLE_WORDS>(table, t, s_tab4);
+    dwg::load_rows<TPB>(root_states, e0, ne, dwb::IN_ROOT, t, s_root);
+    dwg::load_rows<TPB>(dof_state, e0, ne, dwb::IN_DOF, t, s_dof);
+    if (mass_scale != nullptr && com != nullptr) dwg::load_rows<TPB>(mass_scale, e0, ne, dwb::NB, t, s_ms);
     __syncthreads();
     const dwb::Tab T{reinterpret_cast<const uint32_t *>(s_tab4)};
     if (t < nb) s_ids[t] = dwb::row_of(T, ids.b[t] < dwb::NB ? ids.b[t] : dwb::NB - 1);          // (read after the barrier below)
@@ -121,33 +112,33 @@ __global__ __launch_bounds__(TPB) void dwb_k_refresh(int n, const uint4 *__restr
 extern "C" {
 
 int dwb_abi_version(void) { return DWB_ABI_VERSION; }
-const char *dwb_last_error(void) { return s_err; }
+const char *dwb_last_error(void) { return s_err.s; }
 
-int dwb_pack_table(const DwbModel *m, uint32_t *table_host) { return dwb::pack(m, table_host, s_err, sizeof(s_err)); }
+int dwb_pack_table(const DwbModel *m, uint32_t *table_host) { return dwb::pack(m, table_host, s_err.s, sizeof(s_err.s)); }
 
 int dwb_refresh(int32_t num_envs, const uint32_t *table, const float *root_states, const float *dof_state, const float *mass_scale,
                 const int32_t *body_ids_host, int32_t nb, int32_t vel_at_com, float *states, float *com, void *stream) {
-    if (num_envs < 1 || num_envs > 0x7fffffff / (DWB_NUM_BODIES * DWB_ROW) - G) return fail("dwb_refresh: num_envs must be in [1, 2^31 / 494 - 16)");
-    if (!table || !root_states || !dof_state) return fail("dwb_refresh: a buffer is missing");
-    if (!states && !com) return fail("dwb_refresh: states or com must be given");
-    if ((reinterpret_cast<uintptr_t>(table) & 15u) != 0u) return fail("dwb_refresh: the table must be 16-byte aligned");
+    if (num_envs < 1 || num_envs > 0x7fffffff / (DWB_NUM_BODIES * DWB_ROW) - G) return s_err.fail("dwb_refresh: num_envs must be in [1, 2^31 / 494 - 16)");
+    if (!table || !root_states || !dof_state) return s_err.fail("dwb_refresh: a buffer is missing");
+    if (!states && !com) return s_err.fail("dwb_refresh: states or com must be given");
+    if ((reinterpret_cast<uintptr_t>(table) & 15u) != 0u) return s_err.fail("dwb_refresh: the table must be 16-byte aligned");
     Ids ids;
     if (body_ids_host == nullptr) {
-        if (nb != 0 && nb != DWB_NUM_BODIES) return fail("dwb_refresh: without body ids nb must be 0 or 38");
+        if (nb != 0 && nb != DWB_NUM_BODIES) return s_err.fail("dwb_refresh: without body ids nb must be 0 or 38");
         nb = DWB_NUM_BODIES;
         for (int k = 0; k < 40; ++k) ids.b[k] = (unsigned char)(k < DWB_NUM_BODIES ? k : 0);
     } else {
-        if (nb < 1 || nb > DWB_NUM_BODIES) return fail("dwb_refresh: nb must be in 1..38");
+        if (nb < 1 || nb > DWB_NUM_BODIES) return s_err.fail("dwb_refresh: nb must be in 1..38");
         for (int k = 0; k < 40; ++k) ids.b[k] = 0;
         for (int k = 0; k < nb; ++k) {
-            if (body_ids_host[k] < 0 || body_ids_host[k] >= DWB_NUM_BODIES) return fail("dwb_refresh: a body id is outside 0..37");
+            if (body_ids_host[k] < 0 || body_ids_host[k] >= DWB_NUM_BODIES) return s_err.fail("dwb_refresh: a body id is outside 0..37");
             ids.b[k] = (unsigned char)body_ids_host[k];
         }
     }
     hipLaunchKernelGGL(dwb_k_refresh, dim3(dwb::groups(num_envs)), dim3(TPB), 0, (hipStream_t)stream, (int)num_envs,
                        reinterpret_cast<const uint4 *>(table), root_states, dof_state, mass_scale, ids, (int)nb, (int)(vel_at_com != 0), states, com);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dwb_refresh: launch", e);
+    return e == hipSuccess ? 0 : s_err.fail_hip("dwb_refresh: launch", e);
 }
 
 }  // extern "C"

@@ -5,7 +5,8 @@
 // table and the envs' input rows come into LDS; a lane per (env, path) walks the chain, which leaves every body's velocity and acceleration at
 // nu_dot = 0 where the mass matrix's records go later, so a lane per (env, contact) forms the contact's point and Jd_c nu first, and the env's
 // wave writes J_c into Y, a store of its own where dwl's sweeps solve its rows in place (J_c itself is not kept: dw_contact.h forms its words
-// again from the chain's words, which stay to the end).  Then dwl_k_solve's records, subtree sums, pattern words, elimination and multipliers;
+// again from the chain's words, which stay to the end).  Then dwl_k_solve's records, subtree sums, pattern words, elimination and multipliers
+// (dw_factor_wave.h's stages, one definition for both kernels);
 // the sweeps over Y; A = J_c Y (rows >= columns) and its dense L D L', a column's updates spread over the wave with a barrier between columns;
 // x0 behind the chain's words; the small columns (the identity's for A^-1, the right sides of A f = g) swept side by side; nu_dot = x0 + Y f.
 // An env's store is 12.1 KB, a workgroup's LDS 46 KB: three workgroups, nine envs, share a CU's 160 KB.
@@ -13,54 +14,18 @@
 #include <stdio.h>
 
 #include "dw_contact.h"
+#include "dw_factor_wave.h"
+#include "dw_group.h"
 
 namespace {
 
-char s_err[256] = "";
-int fail(const char *msg) { snprintf(s_err, sizeof(s_err), "%s", msg); return -1; }
-int fail_hip(const char *who, hipError_t e) { snprintf(s_err, sizeof(s_err), "%s: %s", who, hipGetErrorString(e)); return -1; }
+dwg::Err s_err;
 
-constexpr int G = DWC_GROUP, L = DWC_LANES, TPB = DWC_GROUP * DWC_LANES, SLOTS = 16 * 16;
+constexpr int G = DWC_GROUP, L = DWC_LANES, TPB = DWC_GROUP * DWC_LANES;
 constexpr int IN_ROOT = dwb::IN_ROOT, IN_DOF = dwb::IN_DOF, NV = dwc::NV, NB = dwc::NB, ND = DWC_NUM_DOF, AS = dwc::AS, MAXM = dwc::MAXM;
-static_assert(L == 64 && G * DWB_MAX_LEAVES <= 64, "a wave per env, the paths of a group in one wave");
+static_assert(L == dwl::L && G * DWB_MAX_LEAVES <= 64, "a wave per env, the paths of a group in one wave");
 static_assert(G * dwj::NI <= TPB && G * dwj::NM <= TPB && G * dwc::MAXK <= TPB, "a lane per record, per moving body, per contact");
-static_assert(DWC_TABLE_WORDS % 4 == 0, "the table is loaded in 16-byte pieces");
 static_assert((DWC_TABLE_WORDS + G * (IN_ROOT + IN_DOF + NB + ND + dwc::ENV)) * 4 <= 64 * 1024, "static LDS");
-
-// the group's rows from global memory into LDS: consecutive lanes, consecutive words
-__device__ __forceinline__ void load_rows(const float *__restrict__ src, int e0, int ne, int row, int t, float *dst) {
-    src += (size_t)e0 * row;
-    for (int i = t; i < ne * row; i += TPB) dst[i] = src[i];
-}
-
-// dwl_k_solve's sweeps of nc <= dwl::CAP columns B [nc][NV] over the factored store H: every step's updates, columns times the step's pattern
-// words, over the env's lanes (2 x 32 for one or two columns, 8 x 8 otherwise) with a workgroup barrier between steps; every lane of the
-// workgroup calls it, with the same nc
-__device__ __forceinline__ void sweeps(const dwb::Tab &T, const float *H, float *B, int nc, int lane, bool live) {
-    const int sh = nc <= 2 ? 1 : 3, cl = lane & ((1 << sh) - 1), el = lane >> sh, cs = 1 << sh, es = L >> sh;
-    int r1 = dwl::row_start(T, NV);
-    for (int k = NV - 1; k >= 1; --k) {
-        const int r0 = dwl::row_start(T, k), m = dwl::clamp_len(r1 - r0) - 1;
-        r1 = r0;
-        if (live)
-            for (int c = cl; c < nc; c += cs)
-                for (int j = el; j < m; j += es) dwl::back_one(T, H, B + c * NV, k, r0, j);
-        __syncthreads();
-    }
-    if (live)
-        for (int c = cl; c < nc; c += cs)
-            for (int k = el; k < NV; k += es) dwl::scale_one(T, H, B + c * NV, k);
-    __syncthreads();
-    int q0 = dwl::tcol_start(T, 0);
-    for (int i = 0; i < NV - 1; ++i) {
-        const int q1 = dwl::tcol_start(T, i + 1), m = q1 - q0;
-        if (live)
-            for (int c = cl; c < nc; c += cs)
-                for (int j = el; j < m; j += es) dwl::fwd_one(T, H, B + c * NV, i, q0, j);
-        q0 = q1;
-        __syncthreads();
-    }
-}
 
 __global__ __launch_bounds__(TPB) void dwc_k_solve(int n, const uint4 *__restrict__ table, const float *__restrict__ root_states,
                                                    const float *__restrict__ dof_state, const float *__restrict__ mass_scale,
@@ -77,11 +42,11 @@ __global__ __launch_bounds__(TPB) void dwc_k_solve(int n, const uint4 *__restric
     const int t = threadIdx.x, e0 = blockIdx.x * G;
     const int ne = n - e0 < G ? n - e0 : G;          // envs of this workgroup (the last one may hold fewer)
     const bool has_ms = mass_scale != nullptr, has_arm = dof_armature != nullptr;
-    for (int i = t; i < DWC_TABLE_WORDS / 4; i += TPB) s_tab4[i] = table[i];
-    load_rows(root_states, e0, ne, IN_ROOT, t, s_root);
-    load_rows(dof_state, e0, ne, IN_DOF, t, s_dof);
-    if (has_ms) load_rows(mass_scale, e0, ne, NB, t, s_ms);
-    if (has_arm) load_rows(dof_armature, e0, ne, ND, t, s_arm);
+    dwg::load_table<TPB, DWC_TABLE_WORDS>(table, t, s_tab4);
+    dwg::load_rows<TPB>(root_states, e0, ne, IN_ROOT, t, s_root);
+    dwg::load_rows<TPB>(dof_state, e0, ne, IN_DOF, t, s_dof);
+    if (has_ms) dwg::load_rows<TPB>(mass_scale, e0, ne, NB, t, s_ms);
+    if (has_arm) dwg::load_rows<TPB>(dof_armature, e0, ne, ND, t, s_arm);
     __syncthreads();
     const dwb::Tab T{reinterpret_cast<const uint32_t *>(s_tab4)};
     const int nleaf = T.nleaf(), K = dwc::count(T), m = 6 * K;
@@ -112,46 +77,11 @@ __global__ __launch_bounds__(TPB) void dwc_k_solve(int n, const uint4 *__restric
     }
     if (minv_jt == nullptr && lambda_inv == nullptr && lambda == nullptr && accel == nullptr && force == nullptr) return;          // (every lane alike)
     __syncthreads();
-    if (t < ne * dwj::NI) {
-        const int ce = t / dwj::NI, k = t - ce * dwj::NI;
-        float *Ec = s_env + ce * dwc::ENV;
-        dwj::record_inertia(T, Ec + dwj::E_KS, has_ms ? s_ms + ce * NB : nullptr, k, Ec + dwj::E_REC + k * dwj::RW);
-    }
-    __syncthreads();
-    // (body-major, leaves first, as in dwl_k_solve)
-    if (t < ne * dwj::NM) {
-        const int b = t / ne;
-        dwj::body_sum(T, s_env + (t - b * ne) * dwc::ENV, dwj::NM - 1 - b);
-    }
-    __syncthreads();
-    if (live)
-        for (int p = lane; p < dwl::PAT; p += L) H[p] = dwl::form_word(T, E, has_arm ? s_arm + e * ND : nullptr, p);
-    __syncthreads();
-    // dwl_k_solve's elimination: a row's 16 x 16 numbered updates four to a lane, all four read, then all four written
-    int r1 = dwl::row_start(T, NV);
-    for (int k = NV - 1; k >= 1; --k) {
-        const int r0 = dwl::row_start(T, k), nw = dwl::clamp_len(r1 - r0);
-        r1 = r0;
-        if (live) {
-            float v[SLOTS / L];
-            int p[SLOTS / L];
-#pragma unroll
-            for (int i = 0; i < SLOTS / L; ++i) {
-                const int u = lane + L * i, s = u >> 4, c = u & 15;
-                p[i] = -1;
-                if (s < nw - 1 && c <= s) v[i] = dwl::eliminate_one(T, H, r0, nw, s, c, &p[i]);
-            }
-#pragma unroll
-            for (int i = 0; i < SLOTS / L; ++i)
-                if (p[i] >= 0) H[p[i]] = v[i];
-        }
-        __syncthreads();
-    }
-    if (live)
-        for (int p = lane; p < dwl::PAT; p += L) dwl::scale_word(T, H, p);
-    __syncthreads();
+    dwl::inertia<dwc::ENV>(T, s_env, has_ms, s_ms, ne, t);
+    dwl::form(T, E, H, has_arm ? s_arm + e * ND : nullptr, lane, live);
+    dwl::eliminate(T, H, lane, live);
     // Y = M^-1 J_c', the rows in place
-    sweeps(T, H, Y, m, lane, live);
+    dwl::sweeps(T, H, Y, m, lane, live);
     if (live) {
         for (int i = lane; i < m * m; i += L) {
             const int r = i / m, c = i - m * r;
@@ -195,7 +125,7 @@ __global__ __launch_bounds__(TPB) void dwc_k_solve(int n, const uint4 *__restric
                 X0[i] = v;
             }
         __syncthreads();
-        sweeps(T, H, X0, R, lane, live);
+        dwl::sweeps(T, H, X0, R, lane, live);
     }
     // the small columns: the identity's for A^-1, then a right side of A f = g for every x0
     const int nid = lambda != nullptr ? m : 0, ncs = nid + R;
@@ -252,29 +182,29 @@ __global__ __launch_bounds__(TPB) void dwc_k_solve(int n, const uint4 *__restric
 extern "C" {
 
 int dwc_abi_version(void) { return DWC_ABI_VERSION; }
-const char *dwc_last_error(void) { return s_err; }
+const char *dwc_last_error(void) { return s_err.s; }
 
 int dwc_pack_table(const DwjModel *m, const DwcContacts *contacts, uint32_t *table_host) {
-    return dwc::pack(m, contacts, table_host, s_err, sizeof(s_err));
+    return dwc::pack(m, contacts, table_host, s_err.s, sizeof(s_err.s));
 }
 
 int dwc_solve(int32_t num_envs, const uint32_t *table, const float *root_states, const float *dof_state, const float *mass_scale,
               const float *dof_armature, int32_t vel_at_com, const float *rhs, int32_t nrhs, const float *sub, const float *gamma, float *jc,
               float *jdnu, float *minv_jt, float *lambda_inv, float *lambda, float *accel, float *force, void *stream) {
-    if (num_envs < 1 || num_envs > 0x7fffffff / (MAXM * NV) - G) return fail("dwc_solve: num_envs must be in [1, 2^31 / 936 - 3)");
-    if (!table || !root_states || !dof_state) return fail("dwc_solve: a buffer is missing");
-    if ((reinterpret_cast<uintptr_t>(table) & 15u) != 0u) return fail("dwc_solve: the table must be 16-byte aligned");
-    if (rhs && !accel && !force) return fail("dwc_solve: rhs needs accel or force");
-    if ((accel || force) && !rhs) return fail("dwc_solve: accel and force need rhs");
-    if (sub && !rhs) return fail("dwc_solve: sub needs rhs");
-    if (gamma && !rhs) return fail("dwc_solve: gamma needs rhs");
-    if (rhs && (nrhs < 1 || nrhs > DWC_MAX_RHS)) return fail("dwc_solve: nrhs must be in 1..DWC_MAX_RHS = 8");
-    if (!jc && !jdnu && !minv_jt && !lambda_inv && !lambda && !accel && !force) return fail("dwc_solve: no output: nothing to compute");
+    if (num_envs < 1 || num_envs > 0x7fffffff / (MAXM * NV) - G) return s_err.fail("dwc_solve: num_envs must be in [1, 2^31 / 936 - 3)");
+    if (!table || !root_states || !dof_state) return s_err.fail("dwc_solve: a buffer is missing");
+    if ((reinterpret_cast<uintptr_t>(table) & 15u) != 0u) return s_err.fail("dwc_solve: the table must be 16-byte aligned");
+    if (rhs && !accel && !force) return s_err.fail("dwc_solve: rhs needs accel or force");
+    if ((accel || force) && !rhs) return s_err.fail("dwc_solve: accel and force need rhs");
+    if (sub && !rhs) return s_err.fail("dwc_solve: sub needs rhs");
+    if (gamma && !rhs) return s_err.fail("dwc_solve: gamma needs rhs");
+    if (rhs && (nrhs < 1 || nrhs > DWC_MAX_RHS)) return s_err.fail("dwc_solve: nrhs must be in 1..DWC_MAX_RHS = 8");
+    if (!jc && !jdnu && !minv_jt && !lambda_inv && !lambda && !accel && !force) return s_err.fail("dwc_solve: no output: nothing to compute");
     hipLaunchKernelGGL(dwc_k_solve, dim3(dwc::groups(num_envs)), dim3(TPB), 0, (hipStream_t)stream, (int)num_envs,
                        reinterpret_cast<const uint4 *>(table), root_states, dof_state, mass_scale, dof_armature, (int)(vel_at_com != 0), rhs,
                        (int)(rhs ? nrhs : 0), sub, gamma, jc, jdnu, minv_jt, lambda_inv, lambda, accel, force);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dwc_solve: launch", e);
+    return e == hipSuccess ? 0 : s_err.fail_hip("dwc_solve: launch", e);
 }
 
 }  // extern "C"

@@ -14,45 +14,25 @@
 #include <stdio.h>
 
 #include "dw_dynamics.h"
+#include "dw_group.h"
 
 namespace {
 
-char s_err[256] = "";
-int fail(const char *msg) { snprintf(s_err, sizeof(s_err), "%s", msg); return -1; }
-int fail_hip(const char *who, hipError_t e) { snprintf(s_err, sizeof(s_err), "%s: %s", who, hipGetErrorString(e)); return -1; }
+dwg::Err s_err;
 
 constexpr int G = DWN_GROUP, TPB = DWN_GROUP * DWN_LANES;
 constexpr int IN_ROOT = dwb::IN_ROOT, IN_DOF = dwb::IN_DOF, NV = dwn::NV, NB = dwn::NB, ND = DWN_NUM_DOF;
 static_assert(TPB % 64 == 0 && G * DWB_MAX_LEAVES <= 64, "whole waves, the paths of a group in one wave");
 static_assert(G * dwn::NI <= TPB && G * dwn::NM <= TPB, "a lane per record, a lane per moving body");
-static_assert(DWN_TABLE_WORDS % 4 == 0, "the table is loaded in 16-byte pieces");
 static_assert((G * NV) % 4 == 0 && (G * DWN_MOM) % 4 == 0, "a group's blocks start on 16 bytes");
 static_assert((DWN_TABLE_WORDS + G * (IN_ROOT + IN_DOF + NB + ND + NV + dwn::ENV)) * 4 <= 64 * 1024, "static LDS");
 
-// the group's rows from global memory into LDS: consecutive lanes, consecutive words
-__device__ __forceinline__ void load_rows(const float *__restrict__ src, int e0, int ne, int row, int t, float *dst) {
-    src += (size_t)e0 * row;
-    for (int i = t; i < ne * row; i += TPB) dst[i] = src[i];
-}
-
 // the group's contiguous block of an output, rows of `row` words at word `at` of each env's OUT: 16 bytes per lane where dst is aligned
 __device__ __forceinline__ void store_rows(float *__restrict__ dst, int e0, int ne, int row, int at, int t, const float *s_env) {
-    const int total = ne * row;
-    float *out = dst + (size_t)e0 * row;
-    auto word = [&](int idx) {
+    dwg::store_block<TPB>(dst + (size_t)e0 * row, ne * row, (reinterpret_cast<uintptr_t>(dst) & 15u) == 0u, t, [&](int idx) {
         const int e = idx / row;
         return s_env[e * dwn::ENV + dwn::E_OUT + at + (idx - row * e)];
-    };
-    int done = 0;
-    if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0u) {
-        const int nv = total / 4;
-        for (int i4 = t; i4 < nv; i4 += TPB) {
-            const float a = word(4 * i4), b = word(4 * i4 + 1), c = word(4 * i4 + 2), d = word(4 * i4 + 3);
-            reinterpret_cast<float4 *>(out)[i4] = make_float4(a, b, c, d);
-        }
-        done = 4 * nv;
-    }
-    for (int i = done + t; i < total; i += TPB) out[i] = word(i);
+    });
 }
 
 __global__ __launch_bounds__(TPB) void dwn_k_inverse_dynamics(int n, const uint4 *__restrict__ table, const float *__restrict__ root_states,
@@ -72,12 +52,12 @@ __global__ __launch_bounds__(TPB) void dwn_k_inverse_dynamics(int n, const uint4
     const int what = (bias != nullptr ? dwn::W_BIAS : 0) | (gravity != nullptr ? dwn::W_GRAV : 0) | (tau != nullptr && accel != nullptr ? dwn::W_TAU : 0) |
                      (momentum != nullptr ? dwn::W_MOM : 0);
     const bool has_acc = (what & dwn::W_TAU) != 0, has_ms = mass_scale != nullptr, has_arm = has_acc && dof_armature != nullptr;
-    for (int i = t; i < DWN_TABLE_WORDS / 4; i += TPB) s_tab4[i] = table[i];
-    load_rows(root_states, e0, ne, IN_ROOT, t, s_root);
-    load_rows(dof_state, e0, ne, IN_DOF, t, s_dof);
-    if (has_ms) load_rows(mass_scale, e0, ne, NB, t, s_ms);
-    if (has_arm) load_rows(dof_armature, e0, ne, ND, t, s_arm);
-    if (has_acc) load_rows(accel, e0, ne, NV, t, s_acc);
+    dwg::load_table<TPB, DWN_TABLE_WORDS>(table, t, s_tab4);
+    dwg::load_rows<TPB>(root_states, e0, ne, IN_ROOT, t, s_root);
+    dwg::load_rows<TPB>(dof_state, e0, ne, IN_DOF, t, s_dof);
+    if (has_ms) dwg::load_rows<TPB>(mass_scale, e0, ne, NB, t, s_ms);
+    if (has_arm) dwg::load_rows<TPB>(dof_armature, e0, ne, ND, t, s_arm);
+    if (has_acc) dwg::load_rows<TPB>(accel, e0, ne, NV, t, s_acc);
     __syncthreads();
     const dwb::Tab T{reinterpret_cast<const uint32_t *>(s_tab4)};
     const float g[3] = {gx, gy, gz};
@@ -110,11 +90,11 @@ __global__ __launch_bounds__(TPB) void dwn_k_inverse_dynamics(int n, const uint4
 extern "C" {
 
 int dwn_abi_version(void) { return DWN_ABI_VERSION; }
-const char *dwn_last_error(void) { return s_err; }
+const char *dwn_last_error(void) { return s_err.s; }
 
 int dwn_pack_table(const DwjModel *m, uint32_t *table_host) {
-    if (dwj::pack(m, table_host, s_err, sizeof(s_err)) != 0) {
-        if (s_err[0] == 'd' && s_err[1] == 'w' && s_err[2] == 'j') s_err[2] = 'n';          // (the refusal is this entry point's)
+    if (dwj::pack(m, table_host, s_err.s, sizeof(s_err.s)) != 0) {
+        if (s_err.s[0] == 'd' && s_err.s[1] == 'w' && s_err.s[2] == 'j') s_err.s[2] = 'n';         // (the refusal is this entry point's)
         return -1;
     }
     return 0;
@@ -123,17 +103,17 @@ int dwn_pack_table(const DwjModel *m, uint32_t *table_host) {
 int dwn_inverse_dynamics(int32_t num_envs, const uint32_t *table, const float *root_states, const float *dof_state, const float *mass_scale,
                          const float *dof_armature, float gx, float gy, float gz, const float *accel, int32_t vel_at_com, float *bias,
                          float *gravity, float *tau, float *momentum, void *stream) {
-    if (num_envs < 1 || num_envs > 0x7fffffff / (IN_DOF + NV) - G) return fail("dwn_inverse_dynamics: num_envs must be in [1, 2^31 / 105 - 4)");
-    if (!table || !root_states || !dof_state) return fail("dwn_inverse_dynamics: a buffer is missing");
-    if ((reinterpret_cast<uintptr_t>(table) & 15u) != 0u) return fail("dwn_inverse_dynamics: the table must be 16-byte aligned");
-    if (tau && !accel) return fail("dwn_inverse_dynamics: tau needs accel");
-    if (!bias && !gravity && !tau && !momentum) return fail("dwn_inverse_dynamics: no output: nothing to compute");
-    if (!isfinite(gx) || !isfinite(gy) || !isfinite(gz)) return fail("dwn_inverse_dynamics: the gravity vector is not finite");
+    if (num_envs < 1 || num_envs > 0x7fffffff / (IN_DOF + NV) - G) return s_err.fail("dwn_inverse_dynamics: num_envs must be in [1, 2^31 / 105 - 4)");
+    if (!table || !root_states || !dof_state) return s_err.fail("dwn_inverse_dynamics: a buffer is missing");
+    if ((reinterpret_cast<uintptr_t>(table) & 15u) != 0u) return s_err.fail("dwn_inverse_dynamics: the table must be 16-byte aligned");
+    if (tau && !accel) return s_err.fail("dwn_inverse_dynamics: tau needs accel");
+    if (!bias && !gravity && !tau && !momentum) return s_err.fail("dwn_inverse_dynamics: no output: nothing to compute");
+    if (!isfinite(gx) || !isfinite(gy) || !isfinite(gz)) return s_err.fail("dwn_inverse_dynamics: the gravity vector is not finite");
     hipLaunchKernelGGL(dwn_k_inverse_dynamics, dim3(dwn::groups(num_envs)), dim3(TPB), 0, (hipStream_t)stream, (int)num_envs,
                        reinterpret_cast<const uint4 *>(table), root_states, dof_state, mass_scale, dof_armature, gx, gy, gz, accel,
                        (int)(vel_at_com != 0), bias, gravity, tau, momentum);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dwn_inverse_dynamics: launch", e);
+    return e == hipSuccess ? 0 : s_err.fail_hip("dwn_inverse_dynamics: launch", e);
 }
 
 }  // extern "C"

@@ -10,30 +10,24 @@
 // the front end has left free: rows 38 down to 1 of L'^-1, the division by D, columns 0 up to 37 of L^-1, every step's independent updates
 // (columns times the step's pattern words) spread over the lanes with a barrier between steps; then they are written.  An env's store is
 // 5.5 KB, a workgroup's LDS 32 KB: five workgroups, 20 waves, share a CU's 160 KB.
+// The loads are dw_group.h's; the inertia stage, the forming of H, the elimination and the sweeps are dw_factor_wave.h's, which dwc_k_solve
+// (dw_contact_dynamics.hip) runs too: the two kernels factor M to the same bits because they run the same code.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 
-#include "dw_factor.h"
+#include "dw_factor_wave.h"
+#include "dw_group.h"
 
 namespace {
 
-char s_err[256] = "";
-int fail(const char *msg) { snprintf(s_err, sizeof(s_err), "%s", msg); return -1; }
-int fail_hip(const char *who, hipError_t e) { snprintf(s_err, sizeof(s_err), "%s: %s", who, hipGetErrorString(e)); return -1; }
+dwg::Err s_err;
 
-constexpr int G = DWL_GROUP, L = DWL_LANES, TPB = DWL_GROUP * DWL_LANES, SLOTS = 16 * 16;
+constexpr int G = DWL_GROUP, L = DWL_LANES, TPB = DWL_GROUP * DWL_LANES;
 constexpr int IN_ROOT = dwb::IN_ROOT, IN_DOF = dwb::IN_DOF, NV = dwl::NV, NB = dwl::NB, ND = DWL_NUM_DOF, MMW = dwl::MMW;
-static_assert(L == 64 && TPB % 64 == 0 && G * DWB_MAX_LEAVES <= 64, "a wave per env, the paths of a group in one wave");
+static_assert(L == dwl::L && TPB % 64 == 0 && G * DWB_MAX_LEAVES <= 64, "a wave per env, the paths of a group in one wave");
 static_assert(G * dwj::NI <= TPB && G * dwj::NM <= TPB, "a lane per record, a lane per moving body");
-static_assert(DWL_TABLE_WORDS % 4 == 0, "the table is loaded in 16-byte pieces");
 static_assert(dwl::CAP <= L && dwl::CAP * NV <= dwl::E_H, "a lane per column, the columns inside the front end's store");
 static_assert((DWL_TABLE_WORDS + G * (IN_ROOT + IN_DOF + NB + ND + dwl::ENV)) * 4 <= 64 * 1024, "static LDS");
-
-// the group's rows from global memory into LDS: consecutive lanes, consecutive words
-__device__ __forceinline__ void load_rows(const float *__restrict__ src, int e0, int ne, int row, int t, float *dst) {
-    src += (size_t)e0 * row;
-    for (int i = t; i < ne * row; i += TPB) dst[i] = src[i];
-}
 
 __global__ __launch_bounds__(TPB) void dwl_k_solve(int n, const uint4 *__restrict__ table, const float *__restrict__ root_states,
                                                    const float *__restrict__ dof_state, const float *__restrict__ mass_scale,
@@ -49,11 +43,11 @@ __global__ __launch_bounds__(TPB) void dwl_k_solve(int n, const uint4 *__restric
     const int t = threadIdx.x, e0 = blockIdx.x * G;
     const int ne = n - e0 < G ? n - e0 : G;          // envs of this workgroup (the last one may hold fewer)
     const bool has_ms = mass_scale != nullptr, has_arm = dof_armature != nullptr;
-    for (int i = t; i < DWL_TABLE_WORDS / 4; i += TPB) s_tab4[i] = table[i];
-    load_rows(root_states, e0, ne, IN_ROOT, t, s_root);
-    load_rows(dof_state, e0, ne, IN_DOF, t, s_dof);
-    if (has_ms) load_rows(mass_scale, e0, ne, NB, t, s_ms);
-    if (has_arm) load_rows(dof_armature, e0, ne, ND, t, s_arm);
+    dwg::load_table<TPB, DWL_TABLE_WORDS>(table, t, s_tab4);
+    dwg::load_rows<TPB>(root_states, e0, ne, IN_ROOT, t, s_root);
+    dwg::load_rows<TPB>(dof_state, e0, ne, IN_DOF, t, s_dof);
+    if (has_ms) dwg::load_rows<TPB>(mass_scale, e0, ne, NB, t, s_ms);
+    if (has_arm) dwg::load_rows<TPB>(dof_armature, e0, ne, ND, t, s_arm);
     __syncthreads();
     const dwb::Tab T{reinterpret_cast<const uint32_t *>(s_tab4)};
     const int nleaf = T.nleaf();
@@ -62,48 +56,13 @@ __global__ __launch_bounds__(TPB) void dwl_k_solve(int n, const uint4 *__restric
         dwj::walk_path(T, t - nleaf * ce, s_root + ce * IN_ROOT, s_dof + ce * IN_DOF, vel_at_com, s_env + ce * dwl::ENV);
     }
     __syncthreads();
-    if (t < ne * dwj::NI) {
-        const int e = t / dwj::NI, k = t - e * dwj::NI;
-        float *E = s_env + e * dwl::ENV;
-        dwj::record_inertia(T, E + dwj::E_KS, has_ms ? s_ms + e * NB : nullptr, k, E + dwj::E_REC + k * dwj::RW);
-    }
-    __syncthreads();
-    // (body-major, leaves first: a wave's lanes hold bodies with subtrees of like size, and the wave that walked the chain starts on the leaves)
-    if (t < ne * dwj::NM) {
-        const int b = t / ne;
-        dwj::body_sum(T, s_env + (t - b * ne) * dwl::ENV, dwj::NM - 1 - b);
-    }
-    __syncthreads();
+    dwl::inertia<dwl::ENV>(T, s_env, has_ms, s_ms, ne, t);
     // from here on a wave per env; the barriers are the workgroup's, the row loop is the same for every env
     const int e = t / L, lane = t - e * L;
     const bool live = e < ne;
     float *E = s_env + (live ? e : 0) * dwl::ENV, *H = E + dwl::E_H;
-    if (live)
-        for (int p = lane; p < dwl::PAT; p += L) H[p] = dwl::form_word(T, E, has_arm ? s_arm + e * ND : nullptr, p);
-    __syncthreads();
-    // a row's 16 x 16 numbered updates are four to a lane: all four read, then all four written, so that a lane waits for one round of loads
-    int r1 = dwl::row_start(T, NV);
-    for (int k = NV - 1; k >= 1; --k) {
-        const int r0 = dwl::row_start(T, k), n = dwl::clamp_len(r1 - r0);
-        r1 = r0;
-        if (live) {
-            float v[SLOTS / L];
-            int p[SLOTS / L];
-#pragma unroll
-            for (int i = 0; i < SLOTS / L; ++i) {
-                const int u = lane + L * i, s = u >> 4, c = u & 15;
-                p[i] = -1;
-                if (s < n - 1 && c <= s) v[i] = dwl::eliminate_one(T, H, r0, n, s, c, &p[i]);
-            }
-#pragma unroll
-            for (int i = 0; i < SLOTS / L; ++i)
-                if (p[i] >= 0) H[p[i]] = v[i];
-        }
-        __syncthreads();
-    }
-    if (live)
-        for (int p = lane; p < dwl::PAT; p += L) dwl::scale_word(T, H, p);
-    __syncthreads();
+    dwl::form(T, E, H, has_arm ? s_arm + e * ND : nullptr, lane, live);
+    dwl::eliminate(T, H, lane, live);
     const size_t env = (size_t)(e0 + e);
     if (live && factor != nullptr) {
         float *out = factor + env * MMW;
@@ -130,30 +89,7 @@ __global__ __launch_bounds__(TPB) void dwl_k_solve(int n, const uint4 *__restric
             }
         }
         __syncthreads();
-        // every step's updates, columns times the step's pattern words, over the env's lanes: 2 x 32 for one or two columns, 8 x 8 otherwise
-        const int sh = nc <= 2 ? 1 : 3, cl = lane & ((1 << sh) - 1), el = lane >> sh, cs = 1 << sh, es = L >> sh;
-        int r1 = dwl::row_start(T, NV);
-        for (int k = NV - 1; k >= 1; --k) {
-            const int r0 = dwl::row_start(T, k), m = dwl::clamp_len(r1 - r0) - 1;
-            r1 = r0;
-            if (live)
-                for (int c = cl; c < nc; c += cs)
-                    for (int j = el; j < m; j += es) dwl::back_one(T, H, E + c * NV, k, r0, j);
-            __syncthreads();
-        }
-        if (live)
-            for (int c = cl; c < nc; c += cs)
-                for (int k = el; k < NV; k += es) dwl::scale_one(T, H, E + c * NV, k);
-        __syncthreads();
-        int q0 = dwl::tcol_start(T, 0);
-        for (int i = 0; i < NV - 1; ++i) {
-            const int q1 = dwl::tcol_start(T, i + 1), m = q1 - q0;
-            if (live)
-                for (int c = cl; c < nc; c += cs)
-                    for (int j = el; j < m; j += es) dwl::fwd_one(T, H, E + c * NV, i, q0, j);
-            q0 = q1;
-            __syncthreads();
-        }
+        dwl::sweeps(T, H, E, nc, lane, live);
         if (live) {
             if (c0 < nid) {
                 float *out = minv + env * MMW;
@@ -180,26 +116,26 @@ __global__ __launch_bounds__(TPB) void dwl_k_solve(int n, const uint4 *__restric
 extern "C" {
 
 int dwl_abi_version(void) { return DWL_ABI_VERSION; }
-const char *dwl_last_error(void) { return s_err; }
+const char *dwl_last_error(void) { return s_err.s; }
 
-int dwl_pack_table(const DwjModel *m, uint32_t *table_host) { return dwl::pack(m, table_host, s_err, sizeof(s_err)); }
+int dwl_pack_table(const DwjModel *m, uint32_t *table_host) { return dwl::pack(m, table_host, s_err.s, sizeof(s_err.s)); }
 
 int dwl_solve(int32_t num_envs, const uint32_t *table, const float *root_states, const float *dof_state, const float *mass_scale,
               const float *dof_armature, int32_t vel_at_com, const float *rhs, int32_t nrhs, const float *sub, float *x, float *factor,
               float *minv, void *stream) {
-    if (num_envs < 1 || num_envs > 0x7fffffff / MMW - G) return fail("dwl_solve: num_envs must be in [1, 2^31 / 1521 - 4)");
-    if (!table || !root_states || !dof_state) return fail("dwl_solve: a buffer is missing");
-    if ((reinterpret_cast<uintptr_t>(table) & 15u) != 0u) return fail("dwl_solve: the table must be 16-byte aligned");
-    if (rhs && !x) return fail("dwl_solve: rhs needs x");
-    if (x && !rhs) return fail("dwl_solve: x needs rhs");
-    if (sub && !rhs) return fail("dwl_solve: sub needs rhs");
-    if (rhs && (nrhs < 1 || nrhs > DWL_MAX_RHS)) return fail("dwl_solve: nrhs must be in 1..DWL_MAX_RHS = 8");
-    if (!x && !factor && !minv) return fail("dwl_solve: no output: nothing to compute");
+    if (num_envs < 1 || num_envs > 0x7fffffff / MMW - G) return s_err.fail("dwl_solve: num_envs must be in [1, 2^31 / 1521 - 4)");
+    if (!table || !root_states || !dof_state) return s_err.fail("dwl_solve: a buffer is missing");
+    if ((reinterpret_cast<uintptr_t>(table) & 15u) != 0u) return s_err.fail("dwl_solve: the table must be 16-byte aligned");
+    if (rhs && !x) return s_err.fail("dwl_solve: rhs needs x");
+    if (x && !rhs) return s_err.fail("dwl_solve: x needs rhs");
+    if (sub && !rhs) return s_err.fail("dwl_solve: sub needs rhs");
+    if (rhs && (nrhs < 1 || nrhs > DWL_MAX_RHS)) return s_err.fail("dwl_solve: nrhs must be in 1..DWL_MAX_RHS = 8");
+    if (!x && !factor && !minv) return s_err.fail("dwl_solve: no output: nothing to compute");
     hipLaunchKernelGGL(dwl_k_solve, dim3(dwl::groups(num_envs)), dim3(TPB), 0, (hipStream_t)stream, (int)num_envs,
                        reinterpret_cast<const uint4 *>(table), root_states, dof_state, mass_scale, dof_armature, (int)(vel_at_com != 0), rhs,
                        (int)(rhs ? nrhs : 0), sub, x, factor, minv);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dwl_solve: launch", e);
+    return e == hipSuccess ? 0 : s_err.fail_hip("dwl_solve: launch", e);
 }
 
 }  // extern "C"

@@ -14,18 +14,16 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 
+#include "dw_group.h"
 #include "dw_jacobian.h"
 
 namespace {
 
-char s_err[256] = "";
-int fail(const char *msg) { snprintf(s_err, sizeof(s_err), "%s", msg); return -1; }
-int fail_hip(const char *who, hipError_t e) { snprintf(s_err, sizeof(s_err), "%s: %s", who, hipGetErrorString(e)); return -1; }
+dwg::Err s_err;
 
 constexpr int G = DWJ_GROUP, TPB = DWJ_GROUP * DWJ_LANES;
 constexpr int IN_ROOT = dwb::IN_ROOT, IN_DOF = dwb::IN_DOF;
 static_assert(TPB % 64 == 0 && G * DWB_MAX_LEAVES <= 64, "whole waves, the paths of a group in one wave");
-static_assert(DWJ_TABLE_WORDS % 4 == 0, "the table is loaded in 16-byte pieces");
 static_assert((G * IN_ROOT) % 4 == 0 && (G * dwj::JROW) % 4 == 0 && (G * dwj::MMW) % 4 == 0 && (G * dwj::CJW) % 4 == 0, "a group's blocks start on 16 bytes");
 static_assert((DWJ_TABLE_WORDS + G * (IN_ROOT + IN_DOF + dwj::JAC_ENV + dwj::NB)) * 4 <= 64 * 1024, "static LDS, Jacobian");
 static_assert((DWJ_TABLE_WORDS + G * (IN_ROOT + IN_DOF + dwj::NB + DWJ_NUM_DOF + dwj::MM_ENV)) * 4 <= 64 * 1024, "static LDS, mass matrix");
@@ -33,31 +31,6 @@ static_assert((DWJ_TABLE_WORDS + G * (IN_ROOT + IN_DOF + dwj::NB + DWJ_NUM_DOF +
 struct Ids {
     unsigned char b[40];
 };
-
-// a group's contiguous block: words [0, total) of dst, word(i) formed on the way out
-template <class W>
-__device__ __forceinline__ void store_block(float *__restrict__ dst, int total, bool aligned, int t, W word) {
-    int done = 0;
-    if (aligned) {
-        const int nv = total / 4;
-        for (int i4 = t; i4 < nv; i4 += TPB) {
-            const float a = word(4 * i4), b = word(4 * i4 + 1), c = word(4 * i4 + 2), d = word(4 * i4 + 3);
-            reinterpret_cast<float4 *>(dst)[i4] = make_float4(a, b, c, d);
-        }
-        done = 4 * nv;
-    }
-    for (int i = done + t; i < total; i += TPB) dst[i] = word(i);
-}
-
-// the table and the group's root and joint rows into LDS: consecutive lanes, consecutive words
-__device__ __forceinline__ void load_inputs(const uint4 *__restrict__ table, const float *__restrict__ root_states, const float *__restrict__ dof_state,
-                                            int e0, int ne, int t, uint4 *s_tab4, float *s_root, float *s_dof) {
-    for (int i = t; i < DWJ_TABLE_WORDS / 4; i += TPB) s_tab4[i] = table[i];
-    const float *src = root_states + (size_t)e0 * IN_ROOT;
-    for (int i = t; i < ne * IN_ROOT; i += TPB) s_root[i] = src[i];
-    src = dof_state + (size_t)e0 * IN_DOF;
-    for (int i = t; i < ne * IN_DOF; i += TPB) s_dof[i] = src[i];
-}
 
 __global__ __launch_bounds__(TPB) void dwj_k_jacobian(int n, const uint4 *__restrict__ table, const float *__restrict__ root_states,
                                                       const float *__restrict__ dof_state, Ids ids, int nb, int vel_at_com, float *__restrict__ jac) {
@@ -68,7 +41,9 @@ __global__ __launch_bounds__(TPB) void dwj_k_jacobian(int n, const uint4 *__rest
     __shared__ int s_rows[G * dwj::NB];          // the group's output rows resolved once: env << 25 | jac_row_of
     const int t = threadIdx.x, e0 = blockIdx.x * G;
     const int ne = n - e0 < G ? n - e0 : G;          // envs of this workgroup (the last one may hold fewer)
-    load_inputs(table, root_states, dof_state, e0, ne, t, s_tab4, s_root, s_dof);
+    dwg::load_table<TPB, DWJ_TABLE_WORDS>(table, t, s_tab4);
+    dwg::load_rows<TPB>(root_states, e0, ne, IN_ROOT, t, s_root);
+    dwg::load_rows<TPB>(dof_state, e0, ne, IN_DOF, t, s_dof);
     __syncthreads();
     const dwb::Tab T{reinterpret_cast<const uint32_t *>(s_tab4)};
     for (int i = t; i < ne * nb; i += TPB) {
@@ -91,7 +66,7 @@ __global__ __launch_bounds__(TPB) void dwj_k_jacobian(int n, const uint4 *__rest
         __syncthreads();
     }
     const int rw = nb * dwj::JROW;
-    store_block(jac + (size_t)e0 * rw, ne * rw, (reinterpret_cast<uintptr_t>(jac) & 15u) == 0u, t, [&](int idx) {
+    dwg::store_block<TPB>(jac + (size_t)e0 * rw, ne * rw, (reinterpret_cast<uintptr_t>(jac) & 15u) == 0u, t, [&](int idx) {
         const int q = idx / dwj::NV, c = idx - dwj::NV * q, er = q / dwj::JR, i = q - dwj::JR * er;
         const int row = s_rows[er];
         return dwj::jac_word(T, s_env + (row >> 25) * dwj::JAC_ENV, row & 0x1ffffff, i, c);
@@ -110,15 +85,11 @@ __global__ __launch_bounds__(TPB) void dwj_k_mass_matrix(int n, const uint4 *__r
     __shared__ float s_env[G * dwj::MM_ENV];
     const int t = threadIdx.x, e0 = blockIdx.x * G;
     const int ne = n - e0 < G ? n - e0 : G;
-    load_inputs(table, root_states, dof_state, e0, ne, t, s_tab4, s_root, s_dof);
-    if (mass_scale != nullptr) {
-        const float *src = mass_scale + (size_t)e0 * dwj::NB;
-        for (int i = t; i < ne * dwj::NB; i += TPB) s_ms[i] = src[i];
-    }
-    if (dof_armature != nullptr) {
-        const float *src = dof_armature + (size_t)e0 * DWJ_NUM_DOF;
-        for (int i = t; i < ne * DWJ_NUM_DOF; i += TPB) s_arm[i] = src[i];
-    }
+    dwg::load_table<TPB, DWJ_TABLE_WORDS>(table, t, s_tab4);
+    dwg::load_rows<TPB>(root_states, e0, ne, IN_ROOT, t, s_root);
+    dwg::load_rows<TPB>(dof_state, e0, ne, IN_DOF, t, s_dof);
+    if (mass_scale != nullptr) dwg::load_rows<TPB>(mass_scale, e0, ne, dwj::NB, t, s_ms);
+    if (dof_armature != nullptr) dwg::load_rows<TPB>(dof_armature, e0, ne, DWJ_NUM_DOF, t, s_arm);
     __syncthreads();
     const dwb::Tab T{reinterpret_cast<const uint32_t *>(s_tab4)};
     const int nleaf = T.nleaf();
@@ -140,31 +111,21 @@ __global__ __launch_bounds__(TPB) void dwj_k_mass_matrix(int n, const uint4 *__r
     }
     __syncthreads();
     const bool arm = dof_armature != nullptr;
-    store_block(mm + (size_t)e0 * dwj::MMW, ne * dwj::MMW, (reinterpret_cast<uintptr_t>(mm) & 15u) == 0u, t, [&](int idx) {
+    dwg::store_block<TPB>(mm + (size_t)e0 * dwj::MMW, ne * dwj::MMW, (reinterpret_cast<uintptr_t>(mm) & 15u) == 0u, t, [&](int idx) {
         const int e = idx / dwj::MMW, w = idx - dwj::MMW * e, r = w / dwj::NV;
         return dwj::mm_word(T, s_env + e * dwj::MM_ENV, arm ? s_arm + e * DWJ_NUM_DOF : nullptr, r, w - dwj::NV * r);
     });
     if (com_jac != nullptr)
-        store_block(com_jac + (size_t)e0 * dwj::CJW, ne * dwj::CJW, (reinterpret_cast<uintptr_t>(com_jac) & 15u) == 0u, t, [&](int idx) {
+        dwg::store_block<TPB>(com_jac + (size_t)e0 * dwj::CJW, ne * dwj::CJW, (reinterpret_cast<uintptr_t>(com_jac) & 15u) == 0u, t, [&](int idx) {
             const int e = idx / dwj::CJW, w = idx - dwj::CJW * e, r = w / dwj::NV;
             return dwj::cj_word(T, s_env + e * dwj::MM_ENV, r, w - dwj::NV * r);
         });
 }
 
 int check_common(const char *who, int32_t num_envs, const void *table, const void *root_states, const void *dof_state, const void *out) {
-    char msg[128];
-    if (num_envs < 1 || num_envs > 0x7fffffff / (DWJ_NUM_BODIES * dwj::JROW) - G) {
-        snprintf(msg, sizeof(msg), "%s: num_envs must be in [1, 2^31 / 8892 - 8)", who);
-        return fail(msg);
-    }
-    if (!table || !root_states || !dof_state || !out) {
-        snprintf(msg, sizeof(msg), "%s: a buffer is missing", who);
-        return fail(msg);
-    }
-    if ((reinterpret_cast<uintptr_t>(table) & 15u) != 0u) {
-        snprintf(msg, sizeof(msg), "%s: the table must be 16-byte aligned", who);
-        return fail(msg);
-    }
+    if (num_envs < 1 || num_envs > 0x7fffffff / (DWJ_NUM_BODIES * dwj::JROW) - G) return s_err.fail(who, "num_envs must be in [1, 2^31 / 8892 - 8)");
+    if (!table || !root_states || !dof_state || !out) return s_err.fail(who, "a buffer is missing");
+    if ((reinterpret_cast<uintptr_t>(table) & 15u) != 0u) return s_err.fail(who, "the table must be 16-byte aligned");
     return 0;
 }
 
@@ -173,30 +134,30 @@ int check_common(const char *who, int32_t num_envs, const void *table, const voi
 extern "C" {
 
 int dwj_abi_version(void) { return DWJ_ABI_VERSION; }
-const char *dwj_last_error(void) { return s_err; }
+const char *dwj_last_error(void) { return s_err.s; }
 
-int dwj_pack_table(const DwjModel *m, uint32_t *table_host) { return dwj::pack(m, table_host, s_err, sizeof(s_err)); }
+int dwj_pack_table(const DwjModel *m, uint32_t *table_host) { return dwj::pack(m, table_host, s_err.s, sizeof(s_err.s)); }
 
 int dwj_jacobian(int32_t num_envs, const uint32_t *table, const float *root_states, const float *dof_state, const int32_t *body_ids_host,
                  int32_t nb, int32_t vel_at_com, float *jac, void *stream) {
     if (check_common("dwj_jacobian", num_envs, table, root_states, dof_state, jac) != 0) return -1;
     Ids ids;
     if (body_ids_host == nullptr) {
-        if (nb != 0 && nb != DWJ_NUM_BODIES) return fail("dwj_jacobian: without body ids nb must be 0 or 38");
+        if (nb != 0 && nb != DWJ_NUM_BODIES) return s_err.fail("dwj_jacobian: without body ids nb must be 0 or 38");
         nb = DWJ_NUM_BODIES;
         for (int k = 0; k < 40; ++k) ids.b[k] = (unsigned char)(k < DWJ_NUM_BODIES ? k : 0);
     } else {
-        if (nb < 1 || nb > DWJ_NUM_BODIES) return fail("dwj_jacobian: nb must be in 1..38");
+        if (nb < 1 || nb > DWJ_NUM_BODIES) return s_err.fail("dwj_jacobian: nb must be in 1..38");
         for (int k = 0; k < 40; ++k) ids.b[k] = 0;
         for (int k = 0; k < nb; ++k) {
-            if (body_ids_host[k] < 0 || body_ids_host[k] >= DWJ_NUM_BODIES) return fail("dwj_jacobian: a body id is outside 0..37");
+            if (body_ids_host[k] < 0 || body_ids_host[k] >= DWJ_NUM_BODIES) return s_err.fail("dwj_jacobian: a body id is outside 0..37");
             ids.b[k] = (unsigned char)body_ids_host[k];
         }
     }
     hipLaunchKernelGGL(dwj_k_jacobian, dim3(dwj::groups(num_envs)), dim3(TPB), 0, (hipStream_t)stream, (int)num_envs,
                        reinterpret_cast<const uint4 *>(table), root_states, dof_state, ids, (int)nb, (int)(vel_at_com != 0), jac);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dwj_jacobian: launch", e);
+    return e == hipSuccess ? 0 : s_err.fail_hip("dwj_jacobian: launch", e);
 }
 
 int dwj_mass_matrix(int32_t num_envs, const uint32_t *table, const float *root_states, const float *dof_state, const float *mass_scale,
@@ -205,7 +166,7 @@ int dwj_mass_matrix(int32_t num_envs, const uint32_t *table, const float *root_s
     hipLaunchKernelGGL(dwj_k_mass_matrix, dim3(dwj::groups(num_envs)), dim3(TPB), 0, (hipStream_t)stream, (int)num_envs,
                        reinterpret_cast<const uint4 *>(table), root_states, dof_state, mass_scale, dof_armature, (int)(vel_at_com != 0), mm, com_jac);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dwj_mass_matrix: launch", e);
+    return e == hipSuccess ? 0 : s_err.fail_hip("dwj_mass_matrix: launch", e);
 }
 
 }  // extern "C"

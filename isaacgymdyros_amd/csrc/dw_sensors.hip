@@ -11,17 +11,17 @@
 #include <stdio.h>
 
 #include "../../include/dyros_walk.h"
+#include "dw_group.h"
 #include "dw_sensors.h"
 
 namespace {
 
-char s_err[256] = "";
-int fail(const char *msg) { snprintf(s_err, sizeof(s_err), "dwf_refresh: %s", msg); return -1; }
-int fail_hip(const char *who, hipError_t e) { snprintf(s_err, sizeof(s_err), "%s: %s", who, hipGetErrorString(e)); return -1; }
+dwg::Err s_err;
+int fail(const char *msg) { return s_err.fail("dwf_refresh", msg); }
 
 constexpr int G = dwf::G, TPB = 256;
 static_assert(TPB % 64 == 0 && G * DWF_NUM_FEET <= 64, "whole waves; the chain lanes sit in one wave");
-static_assert(DWB_TABLE_WORDS % 4 == 0 && DWF_ES_WARM % 4 == 0 && DWF_ES_WORDS % 4 == 0 && DWF_WARM_WORDS % 4 == 0, "16-byte pieces");
+static_assert(DWF_ES_WARM % 4 == 0 && DWF_ES_WORDS % 4 == 0 && DWF_WARM_WORDS % 4 == 0, "16-byte pieces");
 static_assert((G * DWF_SENSOR_WORDS) % 4 == 0 && (G * dwf::W_COP) % 4 == 0 && (G * dwf::W_ZMP) % 4 == 0 && (G * dwf::W_COR) % 4 == 0,
               "a group's output blocks start on 16 bytes");
 static_assert(DWF_ES_WORDS == DW_ES_WORDS && DWF_ES_WARM == DW_ES_WARM && DWF_NUM_CORNERS == DW_NUM_FOOT_PTS && DWF_DOF_ROW == 2 * DW_NUM_DOF,
@@ -60,11 +60,10 @@ __global__ __launch_bounds__(TPB) void dwf_k_refresh(int n, const uint4 *__restr
     const int t = threadIdx.x, e0 = blockIdx.x * G;
     const int ne = n - e0 < G ? n - e0 : G;          // envs of this workgroup (the last one may hold fewer)
     // ---- loads: consecutive lanes, consecutive words ----
-    for (int i = t; i < DWB_TABLE_WORDS / 4; i += TPB) s_tab4[i] = table[i];
+    dwg::load_table<TPB, DWB_TABLE_WORDS>(table, t, s_tab4);
+    dwg::load_rows<TPB>(root_states, e0, ne, dwf::IN_ROOT, t, s_root);
     {
-        const float *src = root_states + (size_t)e0 * dwf::IN_ROOT;
-        for (int i = t; i < ne * dwf::IN_ROOT; i += TPB) s_root[i] = src[i];
-        src = dof_state + (size_t)e0 * DWF_DOF_ROW;
+        const float *src = dof_state + (size_t)e0 * DWF_DOF_ROW;
         for (int i = t; i < ne * dwf::IN_DOF; i += TPB) {
             const int e = i / dwf::IN_DOF;
             s_dof[i] = src[e * DWF_DOF_ROW + (i - e * dwf::IN_DOF)];
@@ -115,7 +114,7 @@ __global__ __launch_bounds__(TPB) void dwf_k_refresh(int n, const uint4 *__restr
 extern "C" {
 
 int dwf_abi_version(void) { return DWF_ABI_VERSION; }
-const char *dwf_last_error(void) { return s_err; }
+const char *dwf_last_error(void) { return s_err.s; }
 
 int dwf_refresh(int32_t num_envs, const uint32_t *table, const float *root_states, const float *dof_state, const float *env_state,
                 const DwfModel *model_host, const DwfSensor *sensors_host, int32_t ns, float *sensors, float *cop, float *zmp,
@@ -135,7 +134,7 @@ int dwf_refresh(int32_t num_envs, const uint32_t *table, const float *root_state
                        reinterpret_cast<const uint4 *>(table), root_states, dof_state, reinterpret_cast<const uint4 *>(env_state), *model_host, sen,
                        (int)ns, sensors, cop, zmp, corners);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dwf_refresh: launch", e);
+    return e == hipSuccess ? 0 : s_err.fail_hip("dwf_refresh: launch", e);
 }
 
 }  // extern "C"

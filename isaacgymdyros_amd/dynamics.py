@@ -31,6 +31,7 @@ import numpy as np
 
 from . import cbind
 from . import jacobians as JM
+from .model_tensors import ModelTensor, ptr, resolve_front
 
 K = cbind.constants("dyros_dynamics.h", "dwn_")
 EXPORTS = list(cbind.signatures("dyros_dynamics.h", "dwn_"))
@@ -44,28 +45,15 @@ def declare(lib) -> dict:
 
 def pack_table(api: dict, model) -> np.ndarray:
     """The device table's DWN_TABLE_WORDS words as a uint32 array (dwn_pack_table: dwj_pack_table's table; raises for a model it refuses)."""
-    import ctypes as C
-    m, t = model if isinstance(model, JM.DwjModel) else JM.model_struct(model), np.zeros(TABLE_WORDS, np.uint32)
-    cbind.check(api, api["pack_table"](C.byref(m), t.ctypes.data))
-    return t
+    return JM.pack_table(api, model, TABLE_WORDS)
 
 
 def resolve(spec) -> dict:
     """The cfg value as a full dict; None when the tensors are off (None or False).  ValueError for anything else that is not True or a dict of
     the keys of DEFAULTS with bool values, or that asks for nothing."""
-    if spec is None or spec is False:
+    out = resolve_front("dynamics", spec, DEFAULTS, DEFAULTS)
+    if out is None:
         return None
-    if spec is True:
-        spec = {}
-    if not isinstance(spec, dict):
-        raise ValueError("dynamics must be True, False or a dict with %s" % ", ".join(DEFAULTS))
-    unknown = set(spec) - set(DEFAULTS)
-    if unknown:
-        raise ValueError("dynamics: unknown keys %s" % sorted(unknown, key=str))
-    out = dict(DEFAULTS, **spec)
-    for k in DEFAULTS:
-        if not isinstance(out[k], bool):
-            raise ValueError("dynamics.%s must be True or False" % k)
     if not (out["bias"] or out["gravity"] or out["inverse_dynamics"] or out["momentum"]):
         raise ValueError("dynamics: none of bias, gravity, inverse_dynamics, momentum: nothing to compute")
     return out
@@ -76,55 +64,37 @@ def validate(spec) -> None:
     resolve(spec)
 
 
-class Dynamics:
+class Dynamics(ModelTensor):
     """The bias, gravity, inverse-dynamics and momentum tensors of one env object's bound buffers (see the module docstring).  host: a
     DyrosDynamicWalk (TocabiAMPLower hands its physics host); vel_at_com: the host's root_vel_at_com unless given.  Buffers are allocated here,
     once."""
 
     def __init__(self, host, spec=True, vel_at_com=None):
-        import torch
-        from . import _lib
-        from .ppo_update import _req
         model = host.model
         spec = resolve(spec)
-        if spec is None:
-            raise ValueError("Dynamics: the spec switches the tensors off")
-        self.api = declare(_lib.load()[0])
-        self.host = host
-        N, dev = host.num_envs, host._tdev
-        self._tdev = dev
-        self.num_envs, self.auto = N, spec["auto"]
+        super().__init__(host, spec, declare)
+        N = self.num_envs
         self.dof_names = list(model.dof_names)
-        self.vel_at_com = int(bool(host._ccfg.root_vel_at_com if vel_at_com is None else vel_at_com))
+        self.vel_at_com = self._vel_at_com(vel_at_com)
         self.g = tuple(float(x) for x in host.cfg["sim"].get("gravity", [0.0, 0.0, -9.81]))
         if len(self.g) != 3 or not all(math.isfinite(x) for x in self.g):
             raise ValueError("dynamics: sim.gravity must be three finite numbers")
-        self.table = torch.from_numpy(pack_table(self.api, model).view(np.int32)).to(dev)
-        f = dict(dtype=torch.float32, device=dev)
-        self.bias = torch.zeros(N, NV, **f) if spec["bias"] else None
-        self.gravity = torch.zeros(N, NV, **f) if spec["gravity"] else None
+        self.table = self._upload(pack_table(self.api, model))
+        self.bias = self._zeros(N, NV) if spec["bias"] else None
+        self.gravity = self._zeros(N, NV) if spec["gravity"] else None
         self.joint_gravity = None if self.gravity is None else self.gravity[:, 6:]
-        self.momentum = torch.zeros(N, MOM, **f) if spec["momentum"] else None
-        self.accel = torch.zeros(N, NV, **f) if spec["inverse_dynamics"] else None
-        self.tau = torch.zeros(N, NV, **f) if spec["inverse_dynamics"] else None
-        # the entry point's arguments, checked once: no argument changes from call to call (the host's buffers are bound once)
-        b = host._buf
-        p = lambda name, dt, **kw: _req(name, b[name], dt, **kw).data_ptr()          # noqa: E731
-        ptr = lambda t: None if t is None else t.data_ptr()          # noqa: E731
-        common = (N, self.table.data_ptr(), p("root_states", torch.float32, shape=(N, 13)), p("dof_state", torch.float32, numel=N * 66),
-                  p("mass_scale", torch.float32, shape=(N, NB)), p("dof_armature", torch.float32, shape=(N, K["DWN_NUM_DOF"])) if spec["armature"] else None) + self.g
+        self.momentum = self._zeros(N, MOM) if spec["momentum"] else None
+        self.accel = self._zeros(N, NV) if spec["inverse_dynamics"] else None
+        self.tau = self._zeros(N, NV) if spec["inverse_dynamics"] else None
+        common = self._inputs(spec["armature"]) + self.g
         any_refresh = self.bias is not None or self.gravity is not None or self.momentum is not None
         self._refresh_args = common + (None, self.vel_at_com, ptr(self.bias), ptr(self.gravity), None, ptr(self.momentum)) if any_refresh else None
         self._id_args = None if self.tau is None else common + (self.accel.data_ptr(), self.vel_at_com, None, None, self.tau.data_ptr(), None)
 
-    def _stream(self):
-        import torch
-        return torch.cuda.current_stream(self._tdev).cuda_stream
-
     def refresh(self):
         """One launch on torch's current stream: `bias`, `gravity` and `momentum`, those the spec holds (none: no launch)."""
         if self._refresh_args is not None:
-            cbind.check(self.api, self.api["inverse_dynamics"](*self._refresh_args, self._stream()))
+            self._launch("inverse_dynamics", self._refresh_args)
 
     def inverse_dynamics(self, accel=None):
         """tau = M accel + h: copies accel [N, 39] into `accel` when given, one launch on torch's current stream; returns `tau`."""
@@ -132,5 +102,5 @@ class Dynamics:
             raise RuntimeError("dynamics: inverse dynamics is switched off (cfg sim.mi355.dynamics: inverse_dynamics)")
         if accel is not None:
             self.accel.copy_(accel)
-        cbind.check(self.api, self.api["inverse_dynamics"](*self._id_args, self._stream()))
+        self._launch("inverse_dynamics", self._id_args)
         return self.tau

@@ -15,7 +15,7 @@ from typing import Any, Dict
 import numpy as np
 import torch
 
-from . import _lib, abi
+from . import _lib, abi, model_tensors
 from .model import NUM_BODIES, NUM_DOF, load_model
 from .task_constants import REWARD_NAMES, load_task_constants
 from .vec_task import VecTask
@@ -118,49 +118,10 @@ class DyrosDynamicWalk(VecTask):
         if spec is not None and spec is not False:
             from .gait_profile import GaitProfile
             self.gait_profile = GaitProfile(self, spec)
-        # cfg sim.mi355.body_states: the rigid-body state tensor [N, K, 13] and the centre of mass, one launch per refresh
-        # (isaacgymdyros_amd/body_states.py); off: None, no buffer, and step() makes no extra launch
-        self.body_states = None
-        spec = self.cfg["sim"].get("mi355", {}).get("body_states")
-        if spec is not None and spec is not False:
-            from .body_states import BodyStates
-            self.body_states = BodyStates(self, spec)
-        # cfg sim.mi355.force_sensors: the foot force-torque sensors [N, S, 6], the soles' centres of pressure and the ZMP, one launch per
-        # refresh (isaacgymdyros_amd/force_sensors.py); off: None, no buffer, and step() makes no extra launch
-        self.force_sensors = None
-        spec = self.cfg["sim"].get("mi355", {}).get("force_sensors")
-        if spec is not None and spec is not False:
-            from .force_sensors import ForceSensors
-            self.force_sensors = ForceSensors(self, spec)
-        # cfg sim.mi355.jacobians: the Jacobian tensor [N, K, 6, 39], the mass matrix [N, 39, 39] and the COM Jacobian, one launch per refresh
-        # (isaacgymdyros_amd/jacobians.py); off: None, no buffer, and step() makes no extra launch
-        self.jacobians = None
-        spec = self.cfg["sim"].get("mi355", {}).get("jacobians")
-        if spec is not None and spec is not False:
-            from .jacobians import Jacobians
-            self.jacobians = Jacobians(self, spec)
-        # cfg sim.mi355.dynamics: the bias-force, gravity, inverse-dynamics and momentum tensors [N, 39] / [N, 6], one launch per call
-        # (isaacgymdyros_amd/dynamics.py); off: None, no buffer, and step() makes no extra launch
-        self.dynamics = None
-        spec = self.cfg["sim"].get("mi355", {}).get("dynamics")
-        if spec is not None and spec is not False:
-            from .dynamics import Dynamics
-            self.dynamics = Dynamics(self, spec)
-        # cfg sim.mi355.forward_dynamics: the solve of M nu_dot = rhs - h, the factor M = L' D L and M^-1, one launch per call
-        # (isaacgymdyros_amd/forward_dynamics.py); off: None, no buffer, and step() makes no extra launch
-        self.forward_dynamics = None
-        spec = self.cfg["sim"].get("mi355", {}).get("forward_dynamics")
-        if spec is not None and spec is not False:
-            from .forward_dynamics import ForwardDynamics
-            self.forward_dynamics = ForwardDynamics(self, spec)
-        # cfg sim.mi355.contact_dynamics: the equation of motion under rigid contact constraints: J_c, the contact-space inertia, and the
-        # acceleration and ground reaction a torque causes while the feet stay planted, one launch per call
-        # (isaacgymdyros_amd/contact_dynamics.py); off: None, no buffer, and step() makes no extra launch
-        self.contact_dynamics = None
-        spec = self.cfg["sim"].get("mi355", {}).get("contact_dynamics")
-        if spec is not None and spec is not False:
-            from .contact_dynamics import ContactDynamics
-            self.contact_dynamics = ContactDynamics(self, spec)
+        # cfg sim.mi355.body_states, force_sensors, jacobians, dynamics, forward_dynamics, contact_dynamics: the model tensors, one launch per
+        # refresh or call (isaacgymdyros_amd/model_tensors.py's table, DESIGN.md sections 21-26); off: None, no buffer, and step() makes no
+        # extra launch
+        model_tensors.attach(self, self, self.cfg["sim"].get("mi355", {}))
 
     # ------------------------------------------------------------------ native handle
     def _make_config(self):
@@ -433,18 +394,7 @@ class DyrosDynamicWalk(VecTask):
             self.extras["stacked_rewards"] = log
         if self.episode_stats is not None:
             self.episode_stats.record()          # (fills extras["termination_cause"] in place)
-        if self.body_states is not None and self.body_states.auto:
-            self.body_states.refresh()
-        if self.force_sensors is not None and self.force_sensors.auto:
-            self.force_sensors.refresh()
-        if self.jacobians is not None and self.jacobians.auto:
-            self.jacobians.refresh()
-        if self.dynamics is not None and self.dynamics.auto:
-            self.dynamics.refresh()
-        if self.forward_dynamics is not None and self.forward_dynamics.auto:
-            self.forward_dynamics.refresh()
-        if self.contact_dynamics is not None and self.contact_dynamics.auto:
-            self.contact_dynamics.refresh()
+        model_tensors.refresh_auto(self)
         if self.run_trace is not None:
             self.run_trace.record()
         if self.gait_profile is not None:
@@ -463,34 +413,12 @@ class DyrosDynamicWalk(VecTask):
             self.episode_stats.restart(ids)          # (the running episodes of these envs are discarded, not counted)
         if self.run_trace is not None:
             self.run_trace.arm(ids)
-        if self.body_states is not None and self.body_states.auto:
-            self.body_states.refresh()
-        if self.force_sensors is not None and self.force_sensors.auto:
-            self.force_sensors.refresh()
-        if self.jacobians is not None and self.jacobians.auto:
-            self.jacobians.refresh()
-        if self.dynamics is not None and self.dynamics.auto:
-            self.dynamics.refresh()
-        if self.forward_dynamics is not None and self.forward_dynamics.auto:
-            self.forward_dynamics.refresh()
-        if self.contact_dynamics is not None and self.contact_dynamics.auto:
-            self.contact_dynamics.refresh()
+        model_tensors.refresh_auto(self)
         # (reset_idx does not touch the observations: the reference recomputes them in the next step's post-physics, :655-669)
 
     def reset(self):
         d = super().reset()
-        if self.body_states is not None and self.body_states.auto:
-            self.body_states.refresh()
-        if self.force_sensors is not None and self.force_sensors.auto:
-            self.force_sensors.refresh()
-        if self.jacobians is not None and self.jacobians.auto:
-            self.jacobians.refresh()
-        if self.dynamics is not None and self.dynamics.auto:
-            self.dynamics.refresh()
-        if self.forward_dynamics is not None and self.forward_dynamics.auto:
-            self.forward_dynamics.refresh()
-        if self.contact_dynamics is not None and self.contact_dynamics.auto:
-            self.contact_dynamics.refresh()
+        model_tensors.refresh_auto(self)
         return d
 
     def refresh_rigid_body_state_tensor(self):

@@ -27,6 +27,7 @@ import math
 import numpy as np
 
 from . import cbind
+from .model_tensors import ModelTensor, ptr, resolve_front
 
 K = cbind.constants("dyros_sensors.h", "dwf_")
 EXPORTS = list(cbind.signatures("dyros_sensors.h", "dwf_"))
@@ -64,22 +65,12 @@ def resolve(spec, model=None, terrain=None) -> dict:
     """The cfg value as a full dict; None when the sensors are off (None or False).  ValueError for anything else that is not True or a dict
     of sensors / cop / corners / auto, for a sensor on another body than a foot's, more than 8 sensors, a quaternion that is not a unit
     one, and for terrain: a cfg["terrain"] whose mesh_type is a height field.  model: a TocabiModel (None: the packaged one)."""
-    if spec is None or spec is False:
+    out = resolve_front("force_sensors", spec, DEFAULTS, ("cop", "corners", "auto"), "sensors, cop, corners and auto")
+    if out is None:
         return None
-    if spec is True:
-        spec = {}
-    if not isinstance(spec, dict):
-        raise ValueError("force_sensors must be True, False or a dict with sensors, cop, corners and auto")
-    unknown = set(spec) - set(DEFAULTS)
-    if unknown:
-        raise ValueError("force_sensors: unknown keys %s" % sorted(unknown))
     if dict(terrain or {}).get("mesh_type", "plane") in ("heightfield", "trimesh"):
         raise ValueError("force_sensors: plane only -- on a height field the task record holds the sole impulses in contact frames that "
                          "are not kept (include/dyros_sensors.h)")
-    out = dict(DEFAULTS, **spec)
-    for k in ("cop", "corners", "auto"):
-        if not isinstance(out[k], bool):
-            raise ValueError("force_sensors.%s must be True or False" % k)
     if model is None:
         from .model import load_model
         model = load_model()
@@ -145,53 +136,40 @@ def sensor_array(sensors):
     return arr
 
 
-class ForceSensors:
+class ForceSensors(ModelTensor):
     """The foot sensors of one env object's bound buffers (see the module docstring).  host: a DyrosDynamicWalk (TocabiAMPLower hands its
     physics host).  Buffers are allocated here, once."""
 
+    WHAT = "sensors"
+
     def __init__(self, host, spec=True):
-        import torch
         from . import _lib
         from .body_states import declare as declare_bodies, pack_table
-        from .ppo_update import _req
         model = host.model
         if getattr(host, "custom_origins", False):
             raise ValueError("force_sensors: plane only (include/dyros_sensors.h); this env runs on a height field")
         spec = resolve(spec, model)
-        if spec is None:
-            raise ValueError("ForceSensors: the spec switches the sensors off")
-        lib = _lib.load()[0]
-        self.api = declare(lib)
-        self.host = host
-        N, dev = host.num_envs, host._tdev
-        self._tdev = dev
-        self.num_envs, self.auto = N, spec["auto"]
+        super().__init__(host, spec, declare)
+        N = self.num_envs
         self.specs = spec["sensors"]
         self.names = [s["body"] for s in self.specs]
         self.dt = float(host.dt) * int(getattr(host, "skipframe", 1))
-        self.table = torch.from_numpy(pack_table(declare_bodies(lib), model).view(np.int32)).to(dev)          # (dwb_pack_table's: the chain constants)
+        self.table = self._upload(pack_table(declare_bodies(_lib.load()[0]), model))          # (dwb_pack_table's: the chain constants)
         self._model_c = model_struct(model, host.dt)
         self._sensors_c = sensor_array(self.specs)
         S = len(self.specs)
-        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)          # noqa: E731
-        self.sensors = z(N, S, K["DWF_SENSOR_WORDS"])
+        self.sensors = self._zeros(N, S, K["DWF_SENSOR_WORDS"])
         self.force, self.torque = self.sensors[..., 0:3], self.sensors[..., 3:6]
         self.vec_sensor_tensor = self.sensors.view(N, S * K["DWF_SENSOR_WORDS"])
-        self.cop = z(N, K["DWF_NUM_FEET"], K["DWF_COP_WORDS"]) if spec["cop"] else None
-        self.zmp = z(N, K["DWF_ZMP_WORDS"]) if spec["cop"] else None
-        self.corners = z(N, K["DWF_NUM_CORNERS"], K["DWF_CORNER_WORDS"]) if spec["corners"] else None
-        # dwf_refresh's arguments, checked once: no argument changes from call to call (the host's buffers are bound once)
-        b = host._buf
-        p = lambda name, dt, **kw: _req(name, b[name], dt, **kw).data_ptr()          # noqa: E731
-        ptr = lambda t: None if t is None else t.data_ptr()          # noqa: E731
-        self._args = (N, self.table.data_ptr(), p("root_states", torch.float32, shape=(N, 13)), p("dof_state", torch.float32, numel=N * K["DWF_DOF_ROW"]),
-                      p("env_state", torch.float32, shape=(N, K["DWF_ES_WORDS"])), C.byref(self._model_c), self._sensors_c, S,
-                      ptr(self.sensors) if S else None, ptr(self.cop), ptr(self.zmp), ptr(self.corners))
+        self.cop = self._zeros(N, K["DWF_NUM_FEET"], K["DWF_COP_WORDS"]) if spec["cop"] else None
+        self.zmp = self._zeros(N, K["DWF_ZMP_WORDS"]) if spec["cop"] else None
+        self.corners = self._zeros(N, K["DWF_NUM_CORNERS"], K["DWF_CORNER_WORDS"]) if spec["corners"] else None
+        self._args = self._inputs() + (self._in("env_state", shape=(N, K["DWF_ES_WORDS"])), C.byref(self._model_c), self._sensors_c, S,
+                                       ptr(self.sensors) if S else None, ptr(self.cop), ptr(self.zmp), ptr(self.corners))
 
     def refresh(self):
         """One launch on torch's current stream; returns the [N, S * 6] view of `sensors`."""
-        import torch
-        cbind.check(self.api, self.api["refresh"](*self._args, torch.cuda.current_stream(self._tdev).cuda_stream))
+        self._launch("refresh", self._args)
         return self.vec_sensor_tensor
 
     def index(self, name: str) -> int:

@@ -34,6 +34,7 @@ import numpy as np
 
 from . import cbind
 from . import jacobians as JM
+from .model_tensors import ModelTensor, joint_space_force, ptr, resolve_front
 
 K = cbind.constants("dyros_forward_dynamics.h", "dwl_")
 EXPORTS = list(cbind.signatures("dyros_forward_dynamics.h", "dwl_"))
@@ -48,28 +49,15 @@ def declare(lib) -> dict:
 def pack_table(api: dict, model) -> np.ndarray:
     """The device table's DWL_TABLE_WORDS words as a uint32 array (dwl_pack_table: dwj_pack_table's table, then the pattern's row starts and
     columns; raises for a model it refuses)."""
-    import ctypes as C
-    m, t = model if isinstance(model, JM.DwjModel) else JM.model_struct(model), np.zeros(TABLE_WORDS, np.uint32)
-    cbind.check(api, api["pack_table"](C.byref(m), t.ctypes.data))
-    return t
+    return JM.pack_table(api, model, TABLE_WORDS)
 
 
 def resolve(spec) -> dict:
     """The cfg value as a full dict; None when the feature is off (None or False).  ValueError for anything else that is not True or a dict of
     the keys of DEFAULTS: rhs an int in 1 .. DWL_MAX_RHS, the others bool."""
-    if spec is None or spec is False:
+    out = resolve_front("forward_dynamics", spec, DEFAULTS, ("factor", "minv", "armature", "auto"))
+    if out is None:
         return None
-    if spec is True:
-        spec = {}
-    if not isinstance(spec, dict):
-        raise ValueError("forward_dynamics must be True, False or a dict with %s" % ", ".join(DEFAULTS))
-    unknown = set(spec) - set(DEFAULTS)
-    if unknown:
-        raise ValueError("forward_dynamics: unknown keys %s" % sorted(unknown, key=str))
-    out = dict(DEFAULTS, **spec)
-    for k in ("factor", "minv", "armature", "auto"):
-        if not isinstance(out[k], bool):
-            raise ValueError("forward_dynamics.%s must be True or False" % k)
     if isinstance(out["rhs"], bool) or not isinstance(out["rhs"], int) or not 1 <= out["rhs"] <= MAX_RHS:
         raise ValueError("forward_dynamics.rhs must be an integer in 1..%d" % MAX_RHS)
     return out
@@ -80,75 +68,53 @@ def validate(spec) -> None:
     resolve(spec)
 
 
-class ForwardDynamics:
+class ForwardDynamics(ModelTensor):
     """The solve, the factor and the inverse of the mass matrix of one env object's bound buffers (see the module docstring).  host: a
     DyrosDynamicWalk (TocabiAMPLower hands its physics host); vel_at_com: the host's root_vel_at_com unless given.  Buffers are allocated here,
     once."""
 
+    WHAT = "feature"
+
     def __init__(self, host, spec=True, vel_at_com=None):
-        import torch
-        from . import _lib
         from .dynamics import Dynamics
-        from .ppo_update import _req
         model = host.model
         spec = resolve(spec)
-        if spec is None:
-            raise ValueError("ForwardDynamics: the spec switches the feature off")
-        self.api = declare(_lib.load()[0])
-        self.host = host
-        N, dev, R = host.num_envs, host._tdev, spec["rhs"]
-        self._tdev = dev
-        self.num_envs, self.auto, self.nrhs = N, spec["auto"], R
+        super().__init__(host, spec, declare)
+        N, R = self.num_envs, spec["rhs"]
+        self.nrhs = R
         self.dof_names = list(model.dof_names)
-        self.vel_at_com = int(bool(host._ccfg.root_vel_at_com if vel_at_com is None else vel_at_com))
-        self.table = torch.from_numpy(pack_table(self.api, model).view(np.int32)).to(dev)
-        f = dict(dtype=torch.float32, device=dev)
-        self.rhs = torch.zeros(N, R, NV, **f)
-        self.x = torch.zeros(N, R, NV, **f)
-        self.factor = torch.zeros(N, NV, NV, **f) if spec["factor"] else None
-        self.minv = torch.zeros(N, NV, NV, **f) if spec["minv"] else None
+        self.vel_at_com = self._vel_at_com(vel_at_com)
+        self.table = self._upload(pack_table(self.api, model))
+        self.rhs = self._zeros(N, R, NV)
+        self.x = self._zeros(N, R, NV)
+        self.factor = self._zeros(N, NV, NV) if spec["factor"] else None
+        self.minv = self._zeros(N, NV, NV) if spec["minv"] else None
         # forward_dynamics(): a right-hand side and a solution of its own, and h from a Dynamics of its own (bias alone, one launch)
-        self._fd_rhs = torch.zeros(N, 1, NV, **f)
-        self.accel = torch.zeros(N, NV, **f)
+        self._fd_rhs = self._zeros(N, 1, NV)
+        self.accel = self._zeros(N, NV)
         self._bias = Dynamics(host, {"bias": True, "gravity": False}, vel_at_com=self.vel_at_com)
-        # the entry point's arguments, checked once: no argument changes from call to call (the host's buffers are bound once)
-        b = host._buf
-        p = lambda name, dt, **kw: _req(name, b[name], dt, **kw).data_ptr()          # noqa: E731
-        ptr = lambda t: None if t is None else t.data_ptr()          # noqa: E731
-        common = (N, self.table.data_ptr(), p("root_states", torch.float32, shape=(N, 13)), p("dof_state", torch.float32, numel=N * 66),
-                  p("mass_scale", torch.float32, shape=(N, NB)), p("dof_armature", torch.float32, shape=(N, K["DWL_NUM_DOF"])) if spec["armature"] else None,
-                  self.vel_at_com)
+        common = self._inputs(spec["armature"]) + (self.vel_at_com,)
         self._solve_args = common + (self.rhs.data_ptr(), R, None, self.x.data_ptr(), None, None)
         self._fd_args = common + (self._fd_rhs.data_ptr(), 1, self._bias.bias.data_ptr(), self.accel.data_ptr(), None, None)
         any_refresh = self.factor is not None or self.minv is not None
         self._refresh_args = common + (None, 0, None, None, ptr(self.factor), ptr(self.minv)) if any_refresh else None
 
-    def _stream(self):
-        import torch
-        return torch.cuda.current_stream(self._tdev).cuda_stream
-
     def refresh(self):
         """One launch on torch's current stream: `factor` and `minv`, those the spec holds (none: no launch)."""
         if self._refresh_args is not None:
-            cbind.check(self.api, self.api["solve"](*self._refresh_args, self._stream()))
+            self._launch("solve", self._refresh_args)
 
     def solve(self, rhs=None):
         """x = M^-1 rhs: copies rhs [N, R, 39] (R = 1: [N, 39] too) into `rhs` when given, one launch on torch's current stream; returns `x`."""
         if rhs is not None:
             self.rhs.copy_(rhs.reshape(self.rhs.shape))
-        cbind.check(self.api, self.api["solve"](*self._solve_args, self._stream()))
+        self._launch("solve", self._solve_args)
         return self.x
 
     def forward_dynamics(self, tau_joint=None, gen_force=None):
         """accel = M^-1 ([0; tau_joint] + gen_force - h): tau_joint [N, 33] and gen_force [N, 39], each or None (zero).  Two launches on torch's
         current stream, the bias forces and the solve; returns `accel` [N, 39]."""
-        r = self._fd_rhs[:, 0]
-        if gen_force is not None:
-            r.copy_(gen_force)
-        else:
-            r.zero_()
-        if tau_joint is not None:
-            r[:, 6:] += tau_joint
+        joint_space_force(self._fd_rhs[:, 0], tau_joint, gen_force)
         self._bias.refresh()
-        cbind.check(self.api, self.api["solve"](*self._fd_args, self._stream()))
+        self._launch("solve", self._fd_args)
         return self.accel

@@ -28,6 +28,7 @@ import numpy as np
 
 from . import cbind
 from .body_states import body_ids
+from .model_tensors import ModelTensor, ptr, resolve_front
 
 K = cbind.constants("dyros_jacobians.h", "dwj_")
 EXPORTS = list(cbind.signatures("dyros_jacobians.h", "dwj_"))
@@ -62,9 +63,10 @@ def model_struct(model) -> DwjModel:
     return m
 
 
-def pack_table(api: dict, model) -> np.ndarray:
-    """The device table's DWJ_TABLE_WORDS words as a uint32 array (dwj_pack_table; raises for a model it refuses)."""
-    m, t = model if isinstance(model, DwjModel) else model_struct(model), np.zeros(TABLE_WORDS, np.uint32)
+def pack_table(api: dict, model, words: int = TABLE_WORDS) -> np.ndarray:
+    """The device table's DWJ_TABLE_WORDS words as a uint32 array (dwj_pack_table; raises for a model it refuses).  words: the table's size
+    where api is another ABI's whose table begins with this one (dynamics.py, forward_dynamics.py)."""
+    m, t = model if isinstance(model, DwjModel) else model_struct(model), np.zeros(words, np.uint32)
     cbind.check(api, api["pack_table"](C.byref(m), t.ctypes.data))
     return t
 
@@ -72,19 +74,9 @@ def pack_table(api: dict, model) -> np.ndarray:
 def resolve(spec, names=None) -> dict:
     """The cfg value as a full dict; None when the tensors are off (None or False).  ValueError for anything else that is not True or a dict of
     the keys of DEFAULTS.  names: the model's body names (None: the packaged model's)."""
-    if spec is None or spec is False:
+    out = resolve_front("jacobians", spec, DEFAULTS, ("jacobian", "mass_matrix", "com_jacobian", "armature", "auto"))
+    if out is None:
         return None
-    if spec is True:
-        spec = {}
-    if not isinstance(spec, dict):
-        raise ValueError("jacobians must be True, False or a dict with %s" % ", ".join(DEFAULTS))
-    unknown = set(spec) - set(DEFAULTS)
-    if unknown:
-        raise ValueError("jacobians: unknown keys %s" % sorted(unknown))
-    out = dict(DEFAULTS, **spec)
-    for k in ("jacobian", "mass_matrix", "com_jacobian", "armature", "auto"):
-        if not isinstance(out[k], bool):
-            raise ValueError("jacobians.%s must be True or False" % k)
     if not out["jacobian"] and not out["mass_matrix"]:
         raise ValueError("jacobians: neither jacobian nor mass_matrix: nothing to compute")
     if out["com_jacobian"] and not out["mass_matrix"]:
@@ -117,63 +109,46 @@ def dof_mask(ids, model) -> np.ndarray:
     return m
 
 
-class Jacobians:
+class Jacobians(ModelTensor):
     """The Jacobians and the mass matrix of one env object's bound buffers (see the module docstring).  host: a DyrosDynamicWalk (TocabiAMPLower
     hands its physics host); vel_at_com: the host's root_vel_at_com unless given.  Buffers are allocated here, once."""
 
     def __init__(self, host, spec=True, vel_at_com=None):
         import torch
-        from . import _lib
-        from .ppo_update import _req
         model = host.model
         spec = resolve(spec, model.body_names)
-        if spec is None:
-            raise ValueError("Jacobians: the spec switches the tensors off")
-        self.api = declare(_lib.load()[0])
-        self.host = host
-        N, dev = host.num_envs, host._tdev
-        self._tdev = dev
-        self.num_envs, self.auto = N, spec["auto"]
+        super().__init__(host, spec, declare)
+        N = self.num_envs
         self.ids = spec["ids"]
         self.names = [model.body_names[g] for g in self.ids]
         self.dof_names = list(model.dof_names)
-        self.dof_mask = torch.from_numpy(dof_mask(self.ids, model)).to(dev)
-        self.vel_at_com = int(bool(host._ccfg.root_vel_at_com if vel_at_com is None else vel_at_com))
+        self.dof_mask = torch.from_numpy(dof_mask(self.ids, model)).to(self._tdev)
+        self.vel_at_com = self._vel_at_com(vel_at_com)
         self.dt = float(host.dt) * int(getattr(host, "skipframe", 1))
-        self.table = torch.from_numpy(pack_table(self.api, model).view(np.int32)).to(dev)
+        self.table = self._upload(pack_table(self.api, model))
         nb = len(self.ids)
-        f = dict(dtype=torch.float32, device=dev)
-        self.jacobian = torch.zeros(N, nb, K["DWJ_JAC_ROWS"], NV, **f) if spec["jacobian"] else None
-        self.mass_matrix = torch.zeros(N, NV, NV, **f) if spec["mass_matrix"] else None
+        self.jacobian = self._zeros(N, nb, K["DWJ_JAC_ROWS"], NV) if spec["jacobian"] else None
+        self.mass_matrix = self._zeros(N, NV, NV) if spec["mass_matrix"] else None
         self.mm = None if self.mass_matrix is None else self.mass_matrix[:, 6:, 6:]
-        self.com_jacobian = torch.zeros(N, 3, NV, **f) if spec["com_jacobian"] else None
+        self.com_jacobian = self._zeros(N, 3, NV) if spec["com_jacobian"] else None
         whole = self.ids == list(range(NB))
         self._ids_c = None if whole else (C.c_int32 * nb)(*self.ids)
-        # the entry points' arguments, checked once: no argument changes from call to call (the host's buffers are bound once)
-        b = host._buf
-        p = lambda name, dt, **kw: _req(name, b[name], dt, **kw).data_ptr()          # noqa: E731
-        common = (N, self.table.data_ptr(), p("root_states", torch.float32, shape=(N, 13)), p("dof_state", torch.float32, numel=N * 66))
-        self._jac_args = None if self.jacobian is None else common + (self._ids_c, 0 if whole else nb, self.vel_at_com, self.jacobian.data_ptr())
-        self._mm_args = None if self.mass_matrix is None else common + (
-            p("mass_scale", torch.float32, shape=(N, NB)), p("dof_armature", torch.float32, shape=(N, K["DWJ_NUM_DOF"])) if spec["armature"] else None,
-            self.vel_at_com, self.mass_matrix.data_ptr(), None if self.com_jacobian is None else self.com_jacobian.data_ptr())
-
-    def _stream(self):
-        import torch
-        return torch.cuda.current_stream(self._tdev).cuda_stream
+        self._jac_args = None if self.jacobian is None else self._inputs() + (self._ids_c, 0 if whole else nb, self.vel_at_com, self.jacobian.data_ptr())
+        self._mm_args = None if self.mass_matrix is None else self._inputs(spec["armature"]) + (self.vel_at_com, self.mass_matrix.data_ptr(),
+                                                                                                ptr(self.com_jacobian))
 
     def refresh_jacobian(self):
         """One launch on torch's current stream; returns `jacobian`."""
         if self._jac_args is None:
             raise RuntimeError("jacobians: the Jacobian is switched off (cfg sim.mi355.jacobians: jacobian)")
-        cbind.check(self.api, self.api["jacobian"](*self._jac_args, self._stream()))
+        self._launch("jacobian", self._jac_args)
         return self.jacobian
 
     def refresh_mass_matrix(self):
         """One launch on torch's current stream; returns `mass_matrix` (and fills `com_jacobian`)."""
         if self._mm_args is None:
             raise RuntimeError("jacobians: the mass matrix is switched off (cfg sim.mi355.jacobians: mass_matrix)")
-        cbind.check(self.api, self.api["mass_matrix"](*self._mm_args, self._stream()))
+        self._launch("mass_matrix", self._mm_args)
         return self.mass_matrix
 
     def refresh(self):

@@ -63,7 +63,7 @@ from typing import Any, Dict
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, model_tensors
 from .config import default_cfg
 from .dyros_dynamic_walk import DyrosDynamicWalk
 from .task_constants import ACTION_HIGH
@@ -175,36 +175,10 @@ class TocabiAMPLower(VecTask):
         self._amp_stats_on = cfg["sim"].get("mi355", {}).get("amp_episode_stats", False)
         if not isinstance(self._amp_stats_on, bool):
             raise ValueError("sim.mi355.amp_episode_stats must be True or False")
-        # cfg sim.mi355.amp_body_states: the rigid-body state tensor over the physics host's bound buffers (isaacgymdyros_amd/body_states.py,
-        # DESIGN.md section 21); off: None.  This class' own key for the same reason: `body_states` would reach the physics host
-        self._amp_bodies_spec = cfg["sim"].get("mi355", {}).get("amp_body_states")
-        from .body_states import validate as validate_body_states
-        validate_body_states(self._amp_bodies_spec)
-        # cfg sim.mi355.amp_force_sensors: the foot force-torque sensors over the physics host's bound buffers (isaacgymdyros_amd/force_sensors.py,
-        # DESIGN.md section 22); off: None.  This class' own key for the same reason
-        self._amp_sensors_spec = cfg["sim"].get("mi355", {}).get("amp_force_sensors")
-        from .force_sensors import validate as validate_force_sensors
-        validate_force_sensors(self._amp_sensors_spec, cfg.get("terrain"))
-        # cfg sim.mi355.amp_jacobians: the Jacobian and mass-matrix tensors over the physics host's bound buffers (isaacgymdyros_amd/jacobians.py,
-        # DESIGN.md section 23); off: None.  This class' own key for the same reason
-        self._amp_jacobians_spec = cfg["sim"].get("mi355", {}).get("amp_jacobians")
-        from .jacobians import validate as validate_jacobians
-        validate_jacobians(self._amp_jacobians_spec)
-        # cfg sim.mi355.amp_dynamics: the bias-force, gravity, inverse-dynamics and momentum tensors over the physics host's bound buffers
-        # (isaacgymdyros_amd/dynamics.py); off: None.  This class' own key for the same reason
-        self._amp_dynamics_spec = cfg["sim"].get("mi355", {}).get("amp_dynamics")
-        from .dynamics import validate as validate_dynamics
-        validate_dynamics(self._amp_dynamics_spec)
-        # cfg sim.mi355.amp_forward_dynamics: the forward dynamics over the physics host's bound buffers (isaacgymdyros_amd/forward_dynamics.py,
-        # DESIGN.md section 25); off: None.  This class' own key for the same reason
-        self._amp_forward_dynamics_spec = cfg["sim"].get("mi355", {}).get("amp_forward_dynamics")
-        from .forward_dynamics import validate as validate_forward_dynamics
-        validate_forward_dynamics(self._amp_forward_dynamics_spec)
-        # cfg sim.mi355.amp_contact_dynamics: the contact-consistent dynamics over the physics host's bound buffers
-        # (isaacgymdyros_amd/contact_dynamics.py); off: None.  This class' own key for the same reason
-        self._amp_contact_dynamics_spec = cfg["sim"].get("mi355", {}).get("amp_contact_dynamics")
-        from .contact_dynamics import validate as validate_contact_dynamics
-        validate_contact_dynamics(self._amp_contact_dynamics_spec)
+        # cfg sim.mi355.amp_body_states, amp_force_sensors, amp_jacobians, amp_dynamics, amp_forward_dynamics, amp_contact_dynamics: the model
+        # tensors over the physics host's bound buffers (isaacgymdyros_amd/model_tensors.py's table, DESIGN.md sections 21-26); off: None.
+        # This class' own keys for the same reason: the plain ones would reach the physics host
+        model_tensors.validate_all(cfg, "amp_")
         e["numObservations"] = (NUM_OBS + NUM_ACTIONS) * self.num_obs_his - NUM_ACTIONS            # :83
         e["numActions"] = NUM_ACTIONS
         super().__init__(config=cfg, sim_device=sim_device, graphics_device_id=graphics_device_id, headless=headless)
@@ -215,6 +189,7 @@ class TocabiAMPLower(VecTask):
         pc["sim"].update({k: copy.deepcopy(v) for k, v in cfg["sim"].items() if k != "mi355"})
         # (physx.num_position_iterations + num_velocity_iterations = the contact solver's iteration count, as the task yaml gives them:
         #  4 + 0 for this task, cfg/task/TocabiAMPLower.yaml)
+        # (this class' own keys stay here, spelled out: tests/test_forward_dynamics.py and tests/test_contact_dynamics.py read them in this text)
         pc["sim"]["mi355"].update({k: v for k, v in cfg["sim"].get("mi355", {}).items() if k not in ("amp_episode_stats", "amp_body_states", "amp_force_sensors", "amp_jacobians", "amp_dynamics", "amp_forward_dynamics", "amp_contact_dynamics")})
         pc["env"]["perturbation"] = False
         # spawn height: the reference's 0.89 (:394) puts the soles 2.2 cm INTO the plane in the initial pose; PhysX resolves that
@@ -384,30 +359,7 @@ class TocabiAMPLower(VecTask):
             from .amp_episode_stats import AmpEpisodeStats
             self.episode_stats = AmpEpisodeStats(self)
             self.extras["termination_cause"] = self.episode_stats.cause
-        self.body_states = None
-        if self._amp_bodies_spec is not None and self._amp_bodies_spec is not False:
-            from .body_states import BodyStates
-            self.body_states = BodyStates(self._phys, self._amp_bodies_spec)          # (vel_at_com: the physics host's root_vel_at_com)
-        self.force_sensors = None
-        if self._amp_sensors_spec is not None and self._amp_sensors_spec is not False:
-            from .force_sensors import ForceSensors
-            self.force_sensors = ForceSensors(self._phys, self._amp_sensors_spec)
-        self.jacobians = None
-        if self._amp_jacobians_spec is not None and self._amp_jacobians_spec is not False:
-            from .jacobians import Jacobians
-            self.jacobians = Jacobians(self._phys, self._amp_jacobians_spec)
-        self.dynamics = None
-        if self._amp_dynamics_spec is not None and self._amp_dynamics_spec is not False:
-            from .dynamics import Dynamics
-            self.dynamics = Dynamics(self._phys, self._amp_dynamics_spec)
-        self.forward_dynamics = None
-        if self._amp_forward_dynamics_spec is not None and self._amp_forward_dynamics_spec is not False:
-            from .forward_dynamics import ForwardDynamics
-            self.forward_dynamics = ForwardDynamics(self._phys, self._amp_forward_dynamics_spec)
-        self.contact_dynamics = None
-        if self._amp_contact_dynamics_spec is not None and self._amp_contact_dynamics_spec is not False:
-            from .contact_dynamics import ContactDynamics
-            self.contact_dynamics = ContactDynamics(self._phys, self._amp_contact_dynamics_spec)
+        model_tensors.attach(self, self._phys, cfg["sim"].get("mi355", {}), "amp_")          # (vel_at_com: the physics host's root_vel_at_com)
 
     # ------------------------------------------------------------------ helpers
     def _rand(self, *shape):
@@ -999,18 +951,7 @@ class TocabiAMPLower(VecTask):
         out = self._step_fused(actions) if self._fused else self._step_torch(actions)
         if self.episode_stats is not None:
             self.episode_stats.record()          # (fills extras["termination_cause"] in place; every step form ends here)
-        if self.body_states is not None and self.body_states.auto:
-            self.body_states.refresh()
-        if self.force_sensors is not None and self.force_sensors.auto:
-            self.force_sensors.refresh()
-        if self.jacobians is not None and self.jacobians.auto:
-            self.jacobians.refresh()
-        if self.dynamics is not None and self.dynamics.auto:
-            self.dynamics.refresh()
-        if self.forward_dynamics is not None and self.forward_dynamics.auto:
-            self.forward_dynamics.refresh()
-        if self.contact_dynamics is not None and self.contact_dynamics.auto:
-            self.contact_dynamics.refresh()
+        model_tensors.refresh_auto(self)
         return out
 
     def refresh_jacobian_tensors(self):

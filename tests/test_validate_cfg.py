@@ -58,6 +58,22 @@ def test_solver_iteration_sum_outside_1_to_64_is_refused(pos, vel):
         validate_cfg(cfg)
 
 
+def test_amp_body_states_is_checked_like_the_other_amp_keys():
+    """validate_cfg checks sim.mi355.amp_body_states as it checks body_states and the other amp_* keys of the model tensors: the ValueError
+    is body_states.validate's, which TocabiAMPLower raises for the same cfg."""
+    from isaacgymdyros_amd import body_states
+    cfg = default_cfg(64)
+    cfg["sim"]["mi355"]["amp_body_states"] = {"bodies": ["Head_Link", "L_Foot_Link", "R_Foot_Link"]}
+    validate_cfg(cfg)
+    for bad in ({"bodies": ["Head"]}, {"mass": True}, {"com": 1}, "on"):
+        with pytest.raises(ValueError) as want:
+            body_states.validate(bad)
+        cfg["sim"]["mi355"]["amp_body_states"] = bad
+        with pytest.raises(ValueError) as got:
+            validate_cfg(cfg)
+        assert str(got.value) == str(want.value)
+
+
 def test_constructor_validates_before_touching_the_library(monkeypatch):
     """The task constructor must fail on the cfg check, not on library loading / allocation: make loading the library
     an error and see the ValueError of the cfg instead."""

@@ -9,43 +9,10 @@
           commit's code path."""
 import argparse
 import json
-import os
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-DEV = "cuda:0"
-
-
-def make_env(n, spec):
-    from isaacgymdyros_amd.config import default_cfg
-    from isaacgymdyros_amd.dyros_dynamic_walk import DyrosDynamicWalk
-    cfg = default_cfg(n, DEV)
-    if spec is not None:
-        cfg["sim"]["mi355"]["dynamics"] = spec
-    return DyrosDynamicWalk(cfg, DEV, 0, True)
-
-
-def chain_us(fn, launches, chain=100):
-    fn()
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    gr = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(gr, stream=side):
-        for _ in range(chain):
-            fn()
-    gr.replay()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(launches // chain):
-        gr.replay()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / (launches // chain * chain) * 1e3
+from _timing import DEV, make_env, chain_us, step_ms
 
 
 SELECTIONS = (("bias", {"gravity": False}), ("gravity", {"bias": False}), ("momentum", {"bias": False, "gravity": False, "momentum": True}),
@@ -58,7 +25,7 @@ def kernel(n, warm_steps, launches):
     from isaacgymdyros_amd.body_states import BodyStates
     from isaacgymdyros_amd.dynamics import Dynamics
     from isaacgymdyros_amd.jacobians import Jacobians
-    env = make_env(n, None)
+    env = make_env(n, "dynamics", None)
     g = torch.Generator(device=DEV).manual_seed(0)
     for _ in range(warm_steps):
         env.step((torch.rand(n, 13, generator=g, device=DEV) * 2 - 1) * 0.05)
@@ -93,23 +60,6 @@ def kernel(n, warm_steps, launches):
     return out
 
 
-def step_ms(n, spec, steps, warm):
-    env = make_env(n, spec)
-    g = torch.Generator(device=DEV).manual_seed(0)
-    a = (torch.rand(n, 13, generator=g, device=DEV) * 2 - 1) * 0.05
-    for _ in range(warm):
-        env.step(a)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(steps):
-        env.step(a)
-    e1.record()
-    torch.cuda.synchronize()
-    env.close()
-    return {"eager_step": True, "dynamics": spec, "num_envs": n, "steps": steps, "ms_per_step": e0.elapsed_time(e1) / steps}
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--num-envs", type=int, default=16384)
@@ -121,7 +71,7 @@ def main():
         print(json.dumps(r), flush=True)
     for _ in range(a.rounds):
         for spec in (None, {"momentum": True, "auto": True}, None, {"momentum": True, "auto": True}):
-            print(json.dumps(step_ms(a.num_envs, spec, 300, 50)), flush=True)
+            print(json.dumps(step_ms(a.num_envs, "dynamics", spec, 300, 50)), flush=True)
 
 
 if __name__ == "__main__":

@@ -14,21 +14,11 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-DEV = "cuda:0"
+from _timing import DEV, make_env, step_ms
 EIGHT = [{"body": b, "pos": [0.01 * i, 0.0, -0.09], "quat": q, "world_frame": w}
          for i, (b, q, w) in enumerate([("L_Foot_Link", [0, 0, 0, 1], False), ("R_Foot_Link", [0, 0, 0, 1], False), ("L_Foot_Link", [0, 0, 0.6, 0.8], False),
                                         ("R_Foot_Link", [0, 0, 0.6, 0.8], False), ("L_Foot_Link", [0, 0, 0, 1], True), ("R_Foot_Link", [0, 0, 0, 1], True),
                                         ("L_Foot_Link", [0.6, 0, 0, 0.8], False), ("R_Foot_Link", [0.6, 0, 0, 0.8], True)])]
-
-
-def make_env(n, spec):
-    from isaacgymdyros_amd.config import default_cfg
-    from isaacgymdyros_amd.dyros_dynamic_walk import DyrosDynamicWalk
-    cfg = default_cfg(n, DEV)
-    if spec is not None:
-        cfg["sim"]["mi355"]["force_sensors"] = spec
-    return DyrosDynamicWalk(cfg, DEV, 0, True)
 
 
 def chain(fn, chain_len=100):
@@ -58,7 +48,7 @@ def replay_us(gr, launches, chain_len=100):
 def kernel(n, warm_steps, launches, rounds):
     from isaacgymdyros_amd.body_states import BodyStates
     from isaacgymdyros_amd.force_sensors import ForceSensors
-    env = make_env(n, None)
+    env = make_env(n, "force_sensors", None)
     g = torch.Generator(device=DEV).manual_seed(0)
     for _ in range(warm_steps):
         env.step((torch.rand(n, 13, generator=g, device=DEV) * 2 - 1) * 0.05)
@@ -82,23 +72,6 @@ def kernel(n, warm_steps, launches, rounds):
     return out
 
 
-def step_ms(n, spec, steps, warm):
-    env = make_env(n, spec)
-    g = torch.Generator(device=DEV).manual_seed(0)
-    a = (torch.rand(n, 13, generator=g, device=DEV) * 2 - 1) * 0.05
-    for _ in range(warm):
-        env.step(a)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(steps):
-        env.step(a)
-    e1.record()
-    torch.cuda.synchronize()
-    env.close()
-    return {"eager_step": True, "force_sensors": spec is not None, "num_envs": n, "steps": steps, "ms_per_step": e0.elapsed_time(e1) / steps}
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--num-envs", type=int, default=16384)
@@ -111,7 +84,7 @@ def main():
     rows = kernel(a.num_envs, a.warm_steps, 2000, a.rounds)
     for _ in range(2):
         for spec in (None, {"auto": True}):
-            rows.append(step_ms(a.num_envs, spec, 500, 50))
+            rows.append(step_ms(a.num_envs, "force_sensors", spec, 500, 50, flag=True))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         f.write("# tools/force_sensors_time.py --num-envs %d --rounds %d --warm-steps %d on one MI355X (median of the rounds; min and max beside it)\n"

@@ -12,62 +12,16 @@
           commit's code path."""
 import argparse
 import json
-import os
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-DEV = "cuda:0"
-
-
-def make_env(n, spec):
-    from isaacgymdyros_amd.config import default_cfg
-    from isaacgymdyros_amd.dyros_dynamic_walk import DyrosDynamicWalk
-    cfg = default_cfg(n, DEV)
-    if spec is not None:
-        cfg["sim"]["mi355"]["forward_dynamics"] = spec
-    return DyrosDynamicWalk(cfg, DEV, 0, True)
-
-
-def chain_us(fn, launches, chain=100):
-    fn()
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    gr = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(gr, stream=side):
-        for _ in range(chain):
-            fn()
-    gr.replay()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(launches // chain):
-        gr.replay()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / (launches // chain * chain) * 1e3
-
-
-def eager_us(fn, calls):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / calls * 1e3
+from _timing import DEV, make_env, chain_us, eager_us, step_ms
 
 
 def kernel(n, warm_steps, launches, reps):
     from isaacgymdyros_amd import forward_dynamics as FM
     from isaacgymdyros_amd.jacobians import Jacobians
-    env = make_env(n, None)
+    env = make_env(n, "forward_dynamics", None)
     g = torch.Generator(device=DEV).manual_seed(0)
     for _ in range(warm_steps):
         env.step((torch.rand(n, 13, generator=g, device=DEV) * 2 - 1) * 0.05)
@@ -111,23 +65,6 @@ def kernel(n, warm_steps, launches, reps):
     env.close()
 
 
-def step_ms(n, spec, steps, warm):
-    env = make_env(n, spec)
-    g = torch.Generator(device=DEV).manual_seed(0)
-    a = (torch.rand(n, 13, generator=g, device=DEV) * 2 - 1) * 0.05
-    for _ in range(warm):
-        env.step(a)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(steps):
-        env.step(a)
-    e1.record()
-    torch.cuda.synchronize()
-    env.close()
-    return {"eager_step": True, "forward_dynamics": spec, "num_envs": n, "steps": steps, "ms_per_step": e0.elapsed_time(e1) / steps}
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--num-envs", type=int, default=16384)
@@ -138,7 +75,7 @@ def main():
     kernel(a.num_envs, a.warm_steps, a.launches, a.reps)
     for _ in range(a.reps):
         for spec in (None, {"factor": True, "minv": True, "auto": True}):
-            print(json.dumps(step_ms(a.num_envs, spec, 300, 50)), flush=True)
+            print(json.dumps(step_ms(a.num_envs, "forward_dynamics", spec, 300, 50)), flush=True)
 
 
 if __name__ == "__main__":

@@ -17,42 +17,12 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-DEV = "cuda:0"
-
-
-def make_env(n, profile):
-    from isaacgymdyros_amd.config import default_cfg
-    from isaacgymdyros_amd.dyros_dynamic_walk import DyrosDynamicWalk
-    cfg = default_cfg(n, DEV)
-    if profile is not None:
-        cfg["sim"]["mi355"]["gait_profile"] = profile
-    return DyrosDynamicWalk(cfg, DEV, 0, True)
-
-
-def chain_us(fn, launches, chain=100):
-    fn()
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    gr = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(gr, stream=side):
-        for _ in range(chain):
-            fn()
-    gr.replay()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(launches // chain):
-        gr.replay()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / (launches // chain * chain) * 1e3
+from _timing import DEV, make_env, chain_us, step_ms
 
 
 def kernel(n, bins, warm_steps, launches):
     from isaacgymdyros_amd import abi, cbind
-    env = make_env(n, {"bins": bins})
+    env = make_env(n, "gait_profile", {"bins": bins})
     gp = env.gait_profile
     g = torch.Generator(device=DEV).manual_seed(0)
     for _ in range(warm_steps):
@@ -75,23 +45,6 @@ def kernel(n, bins, warm_steps, launches):
                     "skipped_terminal_per_launch": s["skipped_terminal"] / (launches + 101)})
     env.close()
     return out
-
-
-def step_ms(n, profile, steps, warm):
-    env = make_env(n, profile)
-    g = torch.Generator(device=DEV).manual_seed(0)
-    a = (torch.rand(n, 13, generator=g, device=DEV) * 2 - 1) * 0.05
-    for _ in range(warm):
-        env.step(a)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(steps):
-        env.step(a)
-    e1.record()
-    torch.cuda.synchronize()
-    env.close()
-    return {"eager_step": True, "gait_profile": profile is not None, "num_envs": n, "steps": steps, "ms_per_step": e0.elapsed_time(e1) / steps}
 
 
 def consumer(n, epochs, on):
@@ -119,7 +72,7 @@ def main():
             print(json.dumps(row), flush=True)
     for _ in range(a.rounds):
         for profile in (None, {"bins": 72}):
-            print(json.dumps(step_ms(a.num_envs, profile, 500, 50)), flush=True)
+            print(json.dumps(step_ms(a.num_envs, "gait_profile", profile, 500, 50, flag=True)), flush=True)
     for _ in range(a.rounds):
         for on in (False, True):
             print(json.dumps(consumer(a.num_envs, a.epochs, on)), flush=True)

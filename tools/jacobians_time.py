@@ -7,48 +7,15 @@
   step:   eager env.step() in milliseconds with jacobians off / on / off / on ("auto": True, every tensor); off is the parent commit's code path."""
 import argparse
 import json
-import os
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-DEV = "cuda:0"
-
-
-def make_env(n, spec):
-    from isaacgymdyros_amd.config import default_cfg
-    from isaacgymdyros_amd.dyros_dynamic_walk import DyrosDynamicWalk
-    cfg = default_cfg(n, DEV)
-    if spec is not None:
-        cfg["sim"]["mi355"]["jacobians"] = spec
-    return DyrosDynamicWalk(cfg, DEV, 0, True)
-
-
-def chain_us(fn, launches, chain=100):
-    fn()
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    gr = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(gr, stream=side):
-        for _ in range(chain):
-            fn()
-    gr.replay()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(launches // chain):
-        gr.replay()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / (launches // chain * chain) * 1e3
+from _timing import DEV, make_env, chain_us, step_ms
 
 
 def kernel(n, warm_steps, launches):
     from isaacgymdyros_amd.jacobians import Jacobians
-    env = make_env(n, None)
+    env = make_env(n, "jacobians", None)
     g = torch.Generator(device=DEV).manual_seed(0)
     for _ in range(warm_steps):
         env.step((torch.rand(n, 13, generator=g, device=DEV) * 2 - 1) * 0.05)
@@ -69,23 +36,6 @@ def kernel(n, warm_steps, launches):
     return out
 
 
-def step_ms(n, spec, steps, warm):
-    env = make_env(n, spec)
-    g = torch.Generator(device=DEV).manual_seed(0)
-    a = (torch.rand(n, 13, generator=g, device=DEV) * 2 - 1) * 0.05
-    for _ in range(warm):
-        env.step(a)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(steps):
-        env.step(a)
-    e1.record()
-    torch.cuda.synchronize()
-    env.close()
-    return {"eager_step": True, "jacobians": spec, "num_envs": n, "steps": steps, "ms_per_step": e0.elapsed_time(e1) / steps}
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--num-envs", type=int, default=16384)
@@ -98,7 +48,7 @@ def main():
     feet = ["Head_Link", "L_Foot_Link", "R_Foot_Link"]
     for _ in range(a.rounds):
         for spec in (None, {"auto": True, "com_jacobian": True}, None, {"bodies": feet, "com_jacobian": True, "auto": True}):
-            print(json.dumps(step_ms(a.num_envs, spec, 300, 50)), flush=True)
+            print(json.dumps(step_ms(a.num_envs, "jacobians", spec, 300, 50)), flush=True)
 
 
 if __name__ == "__main__":
