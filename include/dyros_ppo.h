@@ -73,7 +73,10 @@ extern "C" {
 #define DWP_S_MB         14  /* index of the minibatch the next update takes (as a float)    */
 #define DWP_S_G16        15  /* non-zero: dwp_grad_stats / dwp_adam round dwp_wgrad's summed WEIGHT gradients through fp16 first -- what a backward under
                               * autocast hands unscale_ (inf beyond 65 504, so found_inf and the loss scale move as the reference's would); 0: the
-                              * fp32 sums as they are (default: more bits, found_inf from the fp16 output / activation gradients only)             */
+                              * fp32 sums as they are (default: more bits, found_inf from the fp16 output / activation gradients only).
+                              * Sharded (dwp_grad_bucket): what is rounded is the AVERAGED bucket, after the all-reduce -- the ranks' own gradients
+                              * enter the sum as fp32, so a word beyond 65 504 on one rank whose average is in range is not found.  The biases are
+                              * never rounded.  Parity of this order with the reference's Horovod fp16 path is unpinned.                            */
 #define DWP_S_OUT        16  /* [8] published by dwp_finish: a_loss, c_loss, b_loss, clip fraction, kl, grad norm, scale, skipped (0 or 1) */
 #define DWP_S_WORDS      32
 
@@ -122,7 +125,9 @@ int dwp_grad_stats(const uint16_t *g16, float *gb, float *state, float *part, fl
  * (learning/rl_games_custom/a2c_continuous_seperate.py:171-180, a2c_common_dyros.py:980-981).  Weights: the sum of dwp_wgrad's slabs in
  * dwp_grad_stats' order; biases: the sums over pbuf's buckets, which are cleared as dwp_grad_stats would.  The update then goes on with
  * dwp_grad_stats(NULL, bucket + weights, state, part, NULL, bucket, 1) and dwp_adam_finish(..., gb = bucket + weights, g32 = bucket, 1, ...).
- * With world a power of two the scaling is exact, so a rank alone (world 1) computes the bits of the unsharded update. */
+ * With world a power of two the scaling is exact, so a rank alone (world 1) computes the bits of the unsharded update.
+ * The bucket is fp32 whatever DWP_S_G16 says: with that switch on, dwp_grad_stats / dwp_adam round the AVERAGED weight words through fp16,
+ * after the all-reduce, and leave the bias words alone.  Whether the reference's Horovod fp16 path rounds in that order is unpinned. */
 int dwp_grad_bucket(const float *g32, float *pbuf, float *bucket, float inv_world, void *stream);
 
 /* the Adam step of torch.optim.Adam(fused, capturable; betas (0.9, 0.999), eps 1e-8, no weight decay) behind GradScaler.step, with

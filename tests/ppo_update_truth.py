@@ -255,6 +255,43 @@ def flat(gW1, gW2, gW3, gb1, gb2, gb3):
     return torch.cat([f64(t).reshape(-1) for t in (gW1, gW2, gW3, gb1, gb2, gb3)])
 
 
+def tensor_spans():
+    """[(name, first word, words)] of the six tensors of `flat`; the actor's half of each comes first."""
+    out, o = [], 0
+    for name, n in (("W1", NW1), ("W2", NW2), ("W3", NW3), ("b1", NB1), ("b2", NB2), ("b3", NB3)):
+        out.append((name, o, n))
+        o += n
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ the sharded form: one bucket per rank, their sum
+def rank_bucket(pairs, B, world):
+    """One rank's bucket [weights | biases] as dwp_grad_bucket leaves it: (t, bound) in the layout of `flat`.  pairs: ((dz1, x), (dz2, h1),
+    (dout, h2)) as that rank stored them (x expanded to [2, B, INP]), B its minibatch.  t = the rank's still-scaled gradient / world.  The
+    fp32 sum of the slabs (or of the 32 buckets of a bias) carries its own bound, which the multiply by 1 / world scales with the word; the
+    multiply then rounds once: u32 |t| (nothing at all for a power of two).  fl(1 / 3) itself is a third of an ulp off, 2^-25.6 relative:
+    that is taken from the first term, of which a sum in fp32 uses a small part (its K u32 S counts every addition at full size)."""
+    ts, bs = [], []
+    for dz, a in pairs:
+        g, S = wgrad(dz, a)
+        ts.append(g / world); bs.append(wgrad_sum_bound(S, B) / world)
+    for dz, _ in pairs:
+        g, b = bgrad(dz)
+        ts.append(g / world); bs.append(b / world)
+    t, bound = flat(*ts), flat(*bs)
+    return t, bound + U32 * t.abs()
+
+
+def bucket_sum(buckets):
+    """The all-reduce as the one-GPU tests emulate it: ((b_0 + b_1) + b_2) + ... in ascending rank order -- exact here; R - 1 fp32 additions of
+    partial sums no larger than sum |b_r| add at most (R - 1) u32 sum |b_r| on the GPU.  Returns (sum, that bound)."""
+    bs = [f64(b) for b in buckets]
+    total, mag = bs[0].clone(), bs[0].abs()
+    for b in bs[1:]:
+        total, mag = total + b, mag + b.abs()
+    return total, (len(bs) - 1) * U32 * mag
+
+
 def actor_mask():
     m = torch.zeros(NP, dtype=torch.bool)
     o = 0

@@ -54,9 +54,14 @@ def _snapshot(U, f):
             "growth": st[U.K["DWP_S_GROWTH"]], "steps": [int(st[U.K["DWP_S_STEP"]]), int(st[U.K["DWP_S_STEP"] + 1])], "mb": int(st[U.K["DWP_S_MB"]])}
 
 
-def _check_update(U, case, f, net, batch, snap, worst):
-    """One update of `f`, already run and synchronised, against the helper: every stage from the operands the kernels had."""
-    B, gemm, K = f.B, not f.mfma, U.K
+def _check_gradients(U, case, f, net, batch, snap, worst, left_out=None, sharded=False):
+    """The forward-to-gradient half of one update of `f`, already run and synchronised, against the helper: every stage from the operands the
+    kernels had, up to the slabs' partial weight gradients and the bias gradients.  Returns (the summed weight gradients by layer, the bias
+    gradients' (truth, bound) by layer, the (dz, activation) pairs of the three layers).  left_out: the module's set of samples left out for
+    sitting on the clip boundary (tests/test_ppo_sharded_gpu.py keeps its own, with the same caps).  sharded: dwp_grad_bucket took the bias
+    gradients out of pbuf instead of dwp_grad_stats, so gb holds none (that file holds them in the bucket)."""
+    B, gemm = f.B, not f.mfma
+    left_out = LEFT_OUT if left_out is None else left_out
     mb, scale, W = snap["mb"], snap["scale"], snap["W"]
     sl = slice(mb * B, (mb + 1) * B)
     obs, act, nlp_old, mu_old, adv, ret = (t[sl] for t in batch)
@@ -82,8 +87,8 @@ def _check_update(U, case, f, net, batch, snap, worst):
     L = T.loss(f.out, act, nlp_old, mu_old, adv, ret, net.sigma, scale, C["e_clip"], C["critic_coef"])
     near = (L["margin"].abs() < T.CLIP_MARGIN).nonzero().reshape(-1).tolist()
     for r in near:
-        LEFT_OUT.add((case, mb, r))
-    assert len([k for k in LEFT_OUT if k[0] == case]) <= 1 and len(LEFT_OUT) <= 2, sorted(LEFT_OUT)
+        left_out.add((case, mb, r))
+    assert len([k for k in left_out if k[0] == case]) <= 1 and len(left_out) <= 2, sorted(left_out)
     keep = torch.ones(B, dtype=torch.bool)
     keep[near] = False
     assert lg[0] == pytest.approx(float(L["a_loss"]), rel=1e-5, abs=1e-6) and lg[1] == pytest.approx(float(L["c_loss"]), rel=1e-5)
@@ -127,17 +132,34 @@ def _check_update(U, case, f, net, batch, snap, worst):
         assert float(f.pbuf.abs().max()) == 0.0          # (all 32 buckets of both nets: summed and cleared, also those no workgroup wrote)
     assert float(g_own["W1"][:, :, T.IN:].abs().max()) == 0.0 and float(g_own["W3"][0, T.ACT:].abs().max()) == 0.0 and float(g_own["W3"][1, 1:].abs().max()) == 0.0
     gb = [T.bgrad(dz) for dz in (f.dh1, f.dh2, f.dout)]
-    if not gemm:          # (dwp_grad_stats leaves the buckets' sums in gb; the library-GEMM form's dwp_finish clears it: its biases are held by m, v, p below)
+    if not gemm and not sharded:          # (dwp_grad_stats leaves the buckets' sums in gb; the library-GEMM form's dwp_finish clears it: its biases are held by m, v, p below)
         o = 0
         for name, (t, bound) in zip(("gb1", "gb2", "gb3"), gb):
             got = f.gb[o:o + t.numel()].view(t.shape)
             note(name, got, t, torch.clamp(bound, min=1e-300))
             o += t.numel()
+    return g_own, gb, [(dz, a) for _, dz, a in pairs]
+
+
+def _check_update(U, case, f, net, batch, snap, worst):
+    """One update of `f`, already run and synchronised, against the helper: every stage from the operands the kernels had."""
+    g_own, gb, _ = _check_gradients(U, case, f, net, batch, snap, worst)
     # ---- unscale, clip, Adam, scaler: from the gradients in the fused buffers (bias gradients: the column sums)
     gfull = T.flat(g_own["W1"], g_own["W2"], g_own["W3"], gb[0][0], gb[1][0], gb[2][0])
+    _check_tail(U, f, snap, gfull)          # (these cases are sized not to overflow)
+
+
+def _check_tail(U, f, snap, gfull, found=(False, False)):
+    """The second half of one update of `f`: unscale, clip, Adam and the scaler from the still-scaled gradient `gfull` (the layout of
+    ppo_update_truth.flat) and the snapshot taken before the update.  found: what unscale_'s found_inf must come to, [actor, critic]."""
+    K, mb, scale = U.K, snap["mb"], snap["scale"]
+    lg = f.logged().cpu().tolist()
     R = T.clip_adam(gfull, scale, snap["p"], snap["m"], snap["v"], snap["steps"], LR, C["grad_norm"])
-    assert R["found"] == [False, False] and lg[7] == 0.0          # (these cases are sized not to overflow)
-    assert lg[5] == pytest.approx(R["norm"], rel=1e-4)
+    assert R["found"] == list(found) and lg[7] == float(any(found)) and lg[6] == scale
+    if math.isfinite(R["norm"]):
+        assert lg[5] == pytest.approx(R["norm"], rel=1e-4)
+    else:
+        assert not math.isfinite(lg[5])          # (a non-finite word of the actor's: the logged norm says so too)
     m, v, p = T.f64(f.m), T.f64(f.v), T.f64(f.p)
     assert float((m - R["m"]).abs().max()) <= 1e-5 * float(R["m"].abs().max()) + 1e-12
     assert float((v - R["v"]).abs().max()) <= 1e-4 * float(R["v"].abs().max()) + 1e-20

@@ -127,8 +127,9 @@ def _padded(net):
     return [t.detach().clone() for t in (W1, W2, W3, b1, b2, b3)]
 
 
-def _helper_gradient(P, batch, logstd, scale):
-    """The helper's stages chained (no rounding anywhere: float64 operands): the scaled gradient in the flat layout, and the loss dict."""
+def _helper_gradient(P, batch, logstd, scale, operands=False):
+    """The helper's stages chained (no rounding anywhere: float64 operands): the scaled gradient in the flat layout, and the loss dict
+    (operands: and the three layers' (dz, activation) pairs, what a GPU test reads back from the fused buffers)."""
     W1, W2, W3, b1, b2, b3 = P
     obs, act, old_nlp, old_mu, adv, ret = batch
     x = torch.zeros(obs.shape[0], T.INP, dtype=torch.float64)
@@ -140,8 +141,9 @@ def _helper_gradient(P, batch, logstd, scale):
     d3 = T.dout_of(L)
     dz2 = T.masked(T.linear(d3, W3.transpose(1, 2))[0], h2)
     dz1 = T.masked(T.linear(dz2, W2.transpose(1, 2))[0], h1)
-    g = T.flat(T.wgrad(dz1, x.expand(2, -1, -1))[0], T.wgrad(dz2, h1)[0], T.wgrad(d3, h2)[0], T.bgrad(dz1)[0], T.bgrad(dz2)[0], T.bgrad(d3)[0])
-    return g, L
+    pairs = ((dz1, x.expand(2, -1, -1)), (dz2, h1), (d3, h2))
+    g = T.flat(*[T.wgrad(dz, a)[0] for dz, a in pairs], *[T.bgrad(dz)[0] for dz, _ in pairs])
+    return (g, L, pairs) if operands else (g, L)
 
 
 def test_gradients_clip_and_adam_equal_autograd_clip_grad_norm_and_two_adams():
@@ -216,6 +218,50 @@ def _padded_moments(net, opt_a, opt_c):
     st = dict(opt_a.state)
     st.update(opt_c.state)
     return _padded_like(net, lambda q: st[q]["exp_avg"]), _padded_like(net, lambda q: st[q]["exp_avg_sq"])
+
+
+@pytest.mark.parametrize("R", [2, 3])
+def test_the_average_of_the_ranks_gradients_is_the_gradient_of_the_mean_loss_over_the_union(R):
+    """What the sharded update's "average" means (tests/test_ppo_sharded_gpu.py): R ranks with B_r rows each; float64 autograd on the consumer's
+    own loss functions gives every rank the gradient of ITS mean loss, and the mean of those over the ranks is the gradient of the mean loss
+    over all R B_r rows.  `rank_bucket` is a rank's gradient times the loss scale / R and `bucket_sum` of the ranks' buckets is that
+    average, times the scale; their bounds are first-order sums of |terms| and vanish only where every term does."""
+    B, scale = 32, 512.0
+    net, batch = T.make_case(PPO, R * B, seed=40 + R)
+    net = net.double()
+    batch = [t.double() for t in batch]
+    P = _padded(net)
+
+    def autograd(rows):
+        obs, act, old_nlp, old_mu, adv, ret = (t[rows] for t in batch)
+        mu, logstd, value = net(obs)
+        a_rows, _ = PPO.actor_loss(old_nlp, PPO.neglogp(act, mu, torch.exp(logstd), logstd), adv, C["e_clip"])
+        c_rows = PPO.critic_loss(None, value, C["e_clip"], ret.unsqueeze(1), False)
+        for q in net.parameters():
+            q.grad = None
+        (a_rows.mean() + 0.5 * c_rows.mean() * C["critic_coef"]).backward()
+        return T.flat(*_padded_grads(net))
+    own = [autograd(slice(r * B, (r + 1) * B)) for r in range(R)]
+    union = autograd(slice(0, R * B))
+    average = sum(own) / R
+    assert _same_sums(average, union) and float(union.abs().max()) > 0.0
+    assert not _same_sums(sum(own), union) and not _same_sums(own[0], union)          # (neither the sum nor one rank's own)
+    buckets, bounds = [], []
+    for r in range(R):
+        g, _, pairs = _helper_gradient(P, [t[r * B:(r + 1) * B] for t in batch], net.sigma.double(), scale, operands=True)
+        t, bound = T.rank_bucket(pairs, B, R)
+        assert _same_sums(t, g / R) and _same_sums(t / scale, own[r] / R)
+        assert bool((bound >= T.U32 * t.abs()).all()) and bool(((bound == 0) == (g == 0)).all())
+        buckets.append(t); bounds.append(bound)
+    total, reduce_bound = T.bucket_sum(buckets)
+    assert _same_sums(total / scale, average) and _same_sums(total / scale, union)
+    assert torch.equal(total, sum(buckets[1:], buckets[0])) and torch.equal(reduce_bound, (R - 1) * T.U32 * sum(b.abs() for b in buckets))
+    # the emulated all-reduce in fp32 stays inside its bound
+    got = buckets[0].float()
+    for b in buckets[1:]:
+        got = got + b.float()
+    exact, rb = T.bucket_sum([b.float() for b in buckets])
+    assert bool(((T.f64(got) - exact).abs() <= rb).all())
 
 
 def test_scaler_moves_as_gradscaler_does():
