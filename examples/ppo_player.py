@@ -38,6 +38,9 @@ accel_zero_torque [T, 39] = M^-1 (-h), the acceleration of the unactuated robot 
 contact-consistent dynamics on (isaacgymdyros_amd/contact_dynamics.py) with both feet planted and adds contact_jacobian
 [T, 12, 39], contact_lambda [T, 12, 12] (the contact-space inertia) and contact_force_zero_torque [T, 2, 6], the ground reaction (force, then
 moment about the sensor frame's origin, world axes) the unactuated robot with planted feet would get; without the flag the files are unchanged.
+With --dynamics-inverse it turns the contact inverse dynamics on (isaacgymdyros_amd/contact_inverse_dynamics.py) with both
+feet as contacts and adds hold_torque [T, 33] and hold_force [T, 2, 6]: the joint torques and the foot wrenches that would keep nu_dot = 0 at
+each played state; without the flag the files are unchanged.
 """
 from __future__ import annotations
 
@@ -98,6 +101,8 @@ def run(args):
             cfg["sim"]["mi355"]["forward_dynamics"] = {"minv": True, "auto": True}
         if args.dynamics_contact:
             cfg["sim"]["mi355"]["contact_dynamics"] = {"auto": True}
+        if args.dynamics_inverse:
+            cfg["sim"]["mi355"]["contact_inverse_dynamics"] = {"contact_accel": False, "auto": True}
         os.makedirs(args.dynamics_dir, exist_ok=True)
     env = DyrosDynamicWalk(cfg, args.device, 0, True)
     traces_written = 0
@@ -129,6 +134,10 @@ def run(args):
         rec_cjac = torch.zeros(args.max_steps, dynamics_k, 12, 39, device=dev)
         rec_clam = torch.zeros(args.max_steps, dynamics_k, 12, 12, device=dev)
         rec_cf = torch.zeros(args.max_steps, dynamics_k, 2, 6, device=dev)
+    inverse = bool(dynamics_k and args.dynamics_inverse)
+    if inverse:
+        rec_ht = torch.zeros(args.max_steps, dynamics_k, 33, device=dev)
+        rec_hf = torch.zeros(args.max_steps, dynamics_k, 2, 6, device=dev)
     played = 0
     ck = PK.load(args.checkpoint)
     n_obs, n_act = int(ck["model"][PK.PREFIX + "actor_mlp.0.weight"].shape[1]), int(ck["model"][PK.PREFIX + "mu.weight"].shape[0])
@@ -169,6 +178,9 @@ def run(args):
             rec_cjac[_n].copy_(env.contact_dynamics.jc[:dynamics_k])
             rec_clam[_n].copy_(env.contact_dynamics.lambda_[:dynamics_k])
             rec_cf[_n].copy_(env.contact_dynamics.force[:dynamics_k])
+        if inverse:          # (accel stays zero: what the auto refresh left are the holding torques and wrenches)
+            rec_ht[_n].copy_(env.contact_inverse_dynamics.tau_joint[:dynamics_k])
+            rec_hf[_n].copy_(env.contact_inverse_dynamics.force[:dynamics_k])
         played = _n + 1
         cr += r.view(N)
         steps += 1
@@ -229,6 +241,8 @@ def run(args):
             if contact:
                 more.update(contact_jacobian=rec_cjac[:played, e].cpu().numpy(), contact_lambda=rec_clam[:played, e].cpu().numpy(),
                             contact_force_zero_torque=rec_cf[:played, e].cpu().numpy())
+            if inverse:
+                more.update(hold_torque=rec_ht[:played, e].cpu().numpy(), hold_force=rec_hf[:played, e].cpu().numpy())
             np.savez(os.path.join(args.dynamics_dir, "dynamics_env%d.npz" % e), names=np.asarray(jc.names), dof_names=np.asarray(jc.dof_names),
                      dt=np.float64(jc.dt), jacobian=rec_jac[:played, e].cpu().numpy(), mass_matrix=rec_mm[:played, e].cpu().numpy(),
                      com_jacobian=rec_cj[:played, e].cpu().numpy(), **more)
@@ -270,6 +284,7 @@ def main():
     ap.add_argument("--dynamics-envs", type=int, default=1, help="record envs 0 .. K-1")
     ap.add_argument("--dynamics-accel", action="store_true", help="with --dynamics-dir: add the inverse of the mass matrix and the zero-torque acceleration M^-1 (-h) to each file")
     ap.add_argument("--dynamics-contact", action="store_true", help="with --dynamics-dir: add the feet's contact Jacobian, the contact-space inertia and the zero-torque ground reaction with planted feet to each file")
+    ap.add_argument("--dynamics-inverse", action="store_true", help="with --dynamics-dir: add the joint torques and foot wrenches that would hold nu_dot = 0 at each played state to each file")
     ap.add_argument("--dynamics-forces", action="store_true", help="with --dynamics-dir: add the bias forces, the gravity forces and the momentum to each file")
     ap.add_argument("--device", default="cuda:0")
     run(ap.parse_args())

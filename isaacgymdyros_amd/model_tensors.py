@@ -1,4 +1,4 @@
-"""What the six model-tensor features share on the host (DESIGN.md sections 21-26): the table of the features, by which the env classes and
+"""What the seven model-tensor features share on the host (DESIGN.md sections 21-27): the table of the features, by which the env classes and
 config.validate_cfg validate, attach and refresh them; the common front of their resolve(); and ModelTensor, the base of their classes.
 
 A feature is a module of this package with K, EXPORTS, DEFAULTS, declare, resolve and validate, and a class over one env object's bound
@@ -20,6 +20,7 @@ FEATURES = (
     ("dynamics", "Dynamics", ()),                          # the bias-force, gravity, inverse-dynamics and momentum tensors [N, 39] / [N, 6]
     ("forward_dynamics", "ForwardDynamics", ()),           # the solve of M nu_dot = rhs - h, the factor M = L' D L and M^-1
     ("contact_dynamics", "ContactDynamics", ()),           # the same under rigid contacts: J_c, the contact-space inertia, accelerations and forces
+    ("contact_inverse_dynamics", "ContactInverseDynamics", ()),   # the inverse question: the joint torques and contact wrenches of a wanted acceleration
 )
 
 
