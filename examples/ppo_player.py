@@ -41,6 +41,9 @@ moment about the sensor frame's origin, world axes) the unactuated robot with pl
 With --dynamics-inverse it turns the contact inverse dynamics on (isaacgymdyros_amd/contact_inverse_dynamics.py) with both
 feet as contacts and adds hold_torque [T, 33] and hold_force [T, 2, 6]: the joint torques and the foot wrenches that would keep nu_dot = 0 at
 each played state; without the flag the files are unchanged.
+With --dynamics-stance it turns the stance inverse dynamics on (isaacgymdyros_amd/stance_inverse_dynamics.py) and adds
+stance [T, 2] (which foot the gait's phase loads), stance_torque [T, 33], stance_force [T, 2, 6] and stance_margins [T, 2, 4]: the same
+question under the phase's stance, and how far each loaded sole is from what it can deliver; without the flag the files are unchanged.
 """
 from __future__ import annotations
 
@@ -103,6 +106,8 @@ def run(args):
             cfg["sim"]["mi355"]["contact_dynamics"] = {"auto": True}
         if args.dynamics_inverse:
             cfg["sim"]["mi355"]["contact_inverse_dynamics"] = {"contact_accel": False, "auto": True}
+        if args.dynamics_stance:
+            cfg["sim"]["mi355"]["stance_inverse_dynamics"] = {"contact_accel": False, "base_residual": False}
         os.makedirs(args.dynamics_dir, exist_ok=True)
     env = DyrosDynamicWalk(cfg, args.device, 0, True)
     traces_written = 0
@@ -138,6 +143,12 @@ def run(args):
     if inverse:
         rec_ht = torch.zeros(args.max_steps, dynamics_k, 33, device=dev)
         rec_hf = torch.zeros(args.max_steps, dynamics_k, 2, 6, device=dev)
+    stance = bool(dynamics_k and args.dynamics_stance)
+    if stance:
+        rec_st = torch.zeros(args.max_steps, dynamics_k, 2, dtype=torch.uint8, device=dev)
+        rec_stt = torch.zeros(args.max_steps, dynamics_k, 33, device=dev)
+        rec_stf = torch.zeros(args.max_steps, dynamics_k, 2, 6, device=dev)
+        rec_stm = torch.zeros(args.max_steps, dynamics_k, 2, 4, device=dev)
     played = 0
     ck = PK.load(args.checkpoint)
     n_obs, n_act = int(ck["model"][PK.PREFIX + "actor_mlp.0.weight"].shape[1]), int(ck["model"][PK.PREFIX + "mu.weight"].shape[0])
@@ -181,6 +192,14 @@ def run(args):
         if inverse:          # (accel stays zero: what the auto refresh left are the holding torques and wrenches)
             rec_ht[_n].copy_(env.contact_inverse_dynamics.tau_joint[:dynamics_k])
             rec_hf[_n].copy_(env.contact_inverse_dynamics.force[:dynamics_k])
+        if stance:           # (accel stays zero: the torques and wrenches that hold nu_dot = 0 on the feet the gait's phase loads)
+            sd = env.stance_inverse_dynamics
+            sd.stance_from_phase()
+            sd.refresh()
+            rec_st[_n].copy_(sd.stance[:dynamics_k])
+            rec_stt[_n].copy_(sd.tau_joint[:dynamics_k])
+            rec_stf[_n].copy_(sd.force[:dynamics_k])
+            rec_stm[_n].copy_(sd.margins[:dynamics_k])
         played = _n + 1
         cr += r.view(N)
         steps += 1
@@ -243,6 +262,9 @@ def run(args):
                             contact_force_zero_torque=rec_cf[:played, e].cpu().numpy())
             if inverse:
                 more.update(hold_torque=rec_ht[:played, e].cpu().numpy(), hold_force=rec_hf[:played, e].cpu().numpy())
+            if stance:
+                more.update(stance=rec_st[:played, e].cpu().numpy(), stance_torque=rec_stt[:played, e].cpu().numpy(),
+                            stance_force=rec_stf[:played, e].cpu().numpy(), stance_margins=rec_stm[:played, e].cpu().numpy())
             np.savez(os.path.join(args.dynamics_dir, "dynamics_env%d.npz" % e), names=np.asarray(jc.names), dof_names=np.asarray(jc.dof_names),
                      dt=np.float64(jc.dt), jacobian=rec_jac[:played, e].cpu().numpy(), mass_matrix=rec_mm[:played, e].cpu().numpy(),
                      com_jacobian=rec_cj[:played, e].cpu().numpy(), **more)
@@ -285,6 +307,7 @@ def main():
     ap.add_argument("--dynamics-accel", action="store_true", help="with --dynamics-dir: add the inverse of the mass matrix and the zero-torque acceleration M^-1 (-h) to each file")
     ap.add_argument("--dynamics-contact", action="store_true", help="with --dynamics-dir: add the feet's contact Jacobian, the contact-space inertia and the zero-torque ground reaction with planted feet to each file")
     ap.add_argument("--dynamics-inverse", action="store_true", help="with --dynamics-dir: add the joint torques and foot wrenches that would hold nu_dot = 0 at each played state to each file")
+    ap.add_argument("--dynamics-stance", action="store_true", help="with --dynamics-dir: add the stance of the gait's phase, and the joint torques, foot wrenches and sole margins that would hold nu_dot = 0 under it, to each file")
     ap.add_argument("--dynamics-forces", action="store_true", help="with --dynamics-dir: add the bias forces, the gravity forces and the momentum to each file")
     ap.add_argument("--device", default="cuda:0")
     run(ap.parse_args())
