@@ -27,7 +27,7 @@ SOURCES = [("dw_hip.hip", []),
            ("dw_bodies.hip", ["-ffp-contract=off"]), ("dw_sensors.hip", ["-ffp-contract=off"]),
            ("dw_jacobian.hip", ["-ffp-contract=off"]), ("dw_dynamics.hip", ["-ffp-contract=off"]),
            ("dw_forward_dynamics.hip", ["-ffp-contract=off"]), ("dw_contact_dynamics.hip", ["-ffp-contract=off"]),
-           ("dw_contact_inverse.hip", ["-ffp-contract=off"]), ("dw_stance_inverse.hip", ["-ffp-contract=off"])]
+           ("dw_contact_inverse.hip", ["-ffp-contract=off"])]
 HEADERS = ["dw_wave.h", "dw_devmodel.h", "dw_physics.h", "dw_task.h", "dw_params.h", "dw_quad_wave.h", "dw_quad_model.h",
            "dw_limb.h", "dw_bufg.h", "dw_oct.h", "dw_oct_kernels.h", "dw_oct_post.h", "dw_handle.h", "dw_amp.h", "dw_amp_step.h",
            "dw_amp_motion.h", "dw_stats.h", "dw_amp_stats.h", "dw_trace.h", "dw_meter.h", "dw_gait.h", "dw_bodies.h", "dw_sensors.h", "dw_jacobian.h", "dw_dynamics.h", "dw_factor.h", "dw_contact.h",

@@ -77,6 +77,40 @@ def pack_table(api: dict, model, ids, pos) -> np.ndarray:
     return t
 
 
+def resolve_contacts(cs, names=None, carriers=None, name="contact_dynamics"):
+    """(ids, pos) of a cfg's "contacts"; ValueError under the feature's `name` for what is no list of 1 .. 4 contacts on different moving bodies.
+    names, carriers: the model's body names and body_moving (None: the packaged model's)."""
+    if names is None or carriers is None:
+        from .model import load_model
+        model = load_model()
+        names, carriers = model.body_names, model.body_moving
+    names = list(names)
+    if not isinstance(cs, (list, tuple)) or not 1 <= len(cs) <= MAX_CONTACTS:
+        raise ValueError("%s.contacts must be a list of 1..%d contacts" % (name, MAX_CONTACTS))
+    ids, pos = [], []
+    for c in cs:
+        if not isinstance(c, dict) or "body" not in c or set(c) - {"body", "pos"}:
+            raise ValueError("%s.contacts: a contact is {\"body\": name or Gym id, \"pos\": [x, y, z]}, not %r" % (name, c))
+        b = c["body"]
+        if isinstance(b, str):
+            if b not in names:
+                raise ValueError("%s.contacts: no body named %r" % (name, b))
+            ids.append(names.index(b))
+        elif isinstance(b, (int, np.integer)) and not isinstance(b, bool) and 0 <= int(b) < len(names):
+            ids.append(int(b))
+        else:
+            raise ValueError("%s.contacts: %r is neither a body name nor a Gym id in 0..%d" % (name, b, len(names) - 1))
+        p = c.get("pos", [0.0, 0.0, 0.0])
+        if (isinstance(p, (str, bytes)) or not hasattr(p, "__len__") or len(p) != 3
+                or not all(isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and math.isfinite(v) for v in p)):
+            raise ValueError("%s.contacts: pos must be three finite numbers, not %r" % (name, p))
+        pos.append([float(v) for v in p])
+    moving = [int(carriers[g]) for g in ids]
+    if len(set(moving)) != len(moving):
+        raise ValueError("%s.contacts: two contacts on one moving body: their rows would be dependent" % name)
+    return ids, pos
+
+
 def resolve(spec, names=None, carriers=None) -> dict:
     """The cfg value as a full dict, plus "ids" and "pos" of the contacts; None when the feature is off (None or False).  ValueError for
     anything else that is not True or a dict of the keys of DEFAULTS.  names, carriers: the model's body names and body_moving (None: the
@@ -86,36 +120,7 @@ def resolve(spec, names=None, carriers=None) -> dict:
         return None
     if isinstance(out["rhs"], bool) or not isinstance(out["rhs"], int) or not 1 <= out["rhs"] <= MAX_RHS:
         raise ValueError("contact_dynamics.rhs must be an integer in 1..%d" % MAX_RHS)
-    if names is None or carriers is None:
-        from .model import load_model
-        model = load_model()
-        names, carriers = model.body_names, model.body_moving
-    names = list(names)
-    cs = out["contacts"]
-    if not isinstance(cs, (list, tuple)) or not 1 <= len(cs) <= MAX_CONTACTS:
-        raise ValueError("contact_dynamics.contacts must be a list of 1..%d contacts" % MAX_CONTACTS)
-    ids, pos = [], []
-    for c in cs:
-        if not isinstance(c, dict) or "body" not in c or set(c) - {"body", "pos"}:
-            raise ValueError("contact_dynamics.contacts: a contact is {\"body\": name or Gym id, \"pos\": [x, y, z]}, not %r" % (c,))
-        b = c["body"]
-        if isinstance(b, str):
-            if b not in names:
-                raise ValueError("contact_dynamics.contacts: no body named %r" % (b,))
-            ids.append(names.index(b))
-        elif isinstance(b, (int, np.integer)) and not isinstance(b, bool) and 0 <= int(b) < len(names):
-            ids.append(int(b))
-        else:
-            raise ValueError("contact_dynamics.contacts: %r is neither a body name nor a Gym id in 0..%d" % (b, len(names) - 1))
-        p = c.get("pos", [0.0, 0.0, 0.0])
-        if (isinstance(p, (str, bytes)) or not hasattr(p, "__len__") or len(p) != 3
-                or not all(isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and math.isfinite(v) for v in p)):
-            raise ValueError("contact_dynamics.contacts: pos must be three finite numbers, not %r" % (p,))
-        pos.append([float(v) for v in p])
-    moving = [int(carriers[g]) for g in ids]
-    if len(set(moving)) != len(moving):
-        raise ValueError("contact_dynamics.contacts: two contacts on one moving body: their rows would be dependent")
-    out["ids"], out["pos"] = ids, pos
+    out["ids"], out["pos"] = resolve_contacts(out["contacts"], names, carriers)
     return out
 
 

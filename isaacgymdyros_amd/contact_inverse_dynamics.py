@@ -52,21 +52,30 @@ EXPORTS = list(cbind.signatures("dyros_contact_inverse_dynamics.h", "dwi_"))
 NB, NV, ND, GROUP, MAX_CONTACTS, TABLE_WORDS = K["DWI_NUM_BODIES"], K["DWI_NV"], K["DWI_NUM_DOF"], K["DWI_GROUP"], K["DWI_MAX_CONTACTS"], K["DWI_TABLE_WORDS"]
 DEFAULTS = {"contacts": [{"body": "L_Foot_Link", "pos": [0.0, 0.0, -0.09]}, {"body": "R_Foot_Link", "pos": [0.0, 0.0, -0.09]}], "weights": None,
             "contact_accel": True, "tau_full": False, "armature": True, "auto": False}
+NAME = "contact_inverse_dynamics"          # in the messages; stance_inverse_dynamics.py passes its own
 
 
 def declare(lib) -> dict:
     return cbind.declare(lib, "dyros_contact_inverse_dynamics.h", "dwi_")
 
 
+def table_front(model, ids, pos, weights, name=NAME):
+    """What a pack_table of this table begins with: the model and the contacts as structs, the weights as [6 K] float32 or None (ValueError
+    for another size) and the count they were sized for."""
+    m = model if isinstance(model, JM.DwjModel) else JM.model_struct(model)
+    c = ids if isinstance(ids, CM.DwcContacts) else CM.contacts_struct(ids, pos)
+    n = max(1, min(c.count, MAX_CONTACTS))
+    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
+    if w is not None and w.size != 6 * n:
+        raise ValueError("%s: %d weights for %d contacts" % (name, w.size, c.count))
+    return m, c, w, n
+
+
 def pack_table(api: dict, model, ids, pos, weights=None) -> np.ndarray:
     """The device table's DWI_TABLE_WORDS words as a uint32 array (dwi_pack_table: dwn_pack_table's table, the contacts, the weights [6 K] or
     None for ones; raises for a model, contacts or weights it refuses)."""
     import ctypes as C
-    m, t = model if isinstance(model, JM.DwjModel) else JM.model_struct(model), np.zeros(TABLE_WORDS, np.uint32)
-    c = ids if isinstance(ids, CM.DwcContacts) else CM.contacts_struct(ids, pos)
-    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
-    if w is not None and w.size != 6 * max(1, min(c.count, MAX_CONTACTS)):
-        raise ValueError("contact_inverse_dynamics: %d weights for %d contacts" % (w.size, c.count))
+    (m, c, w, _), t = table_front(model, ids, pos, weights), np.zeros(TABLE_WORDS, np.uint32)
     cbind.check(api, api["pack_table"](C.byref(m), C.byref(c), None if w is None else w.ctypes.data, t.ctypes.data))
     return t
 
@@ -75,11 +84,11 @@ def _number(v) -> bool:
     return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and math.isfinite(v) and v > 0
 
 
-def resolve_weights(weights, count: int):
+def resolve_weights(weights, count: int, name=NAME):
     """None, or the weights as [6 K] floats: six positive numbers (every contact's) or K lists of six.  ValueError otherwise."""
     if weights is None:
         return None
-    bad = ValueError("contact_inverse_dynamics.weights must be None, six finite positive numbers or %d lists of six, not %r" % (count, weights))
+    bad = ValueError("%s.weights must be None, six finite positive numbers or %d lists of six, not %r" % (name, count, weights))
     if isinstance(weights, (str, bytes)) or not hasattr(weights, "__len__") or len(weights) == 0:
         raise bad
     rows = list(weights)
@@ -92,20 +101,19 @@ def resolve_weights(weights, count: int):
     return [float(v) for r in rows for v in r]
 
 
+def resolve_contacts(out: dict, names=None, carriers=None, name=NAME) -> dict:
+    """out with "ids" and "pos" of its "contacts" and "w" (None or [6 K]) of its "weights"; ValueError under `name`."""
+    out["ids"], out["pos"] = CM.resolve_contacts(out["contacts"], names, carriers, name)
+    out["w"] = resolve_weights(out["weights"], len(out["ids"]), name)
+    return out
+
+
 def resolve(spec, names=None, carriers=None) -> dict:
     """The cfg value as a full dict, plus "ids" and "pos" of the contacts and "w" (None or [6 K]); None when the feature is off (None or
     False).  ValueError for anything else that is not True or a dict of the keys of DEFAULTS.  names, carriers: the model's body names and
     body_moving (None: the packaged model's)."""
-    out = resolve_front("contact_inverse_dynamics", spec, DEFAULTS, ("contact_accel", "tau_full", "armature", "auto"))
-    if out is None:
-        return None
-    try:
-        c = CM.resolve({"contacts": out["contacts"]}, names, carriers)
-    except ValueError as e:
-        raise ValueError(str(e).replace("contact_dynamics", "contact_inverse_dynamics", 1)) from None
-    out["ids"], out["pos"] = c["ids"], c["pos"]
-    out["w"] = resolve_weights(out["weights"], len(out["ids"]))
-    return out
+    out = resolve_front(NAME, spec, DEFAULTS, ("contact_accel", "tau_full", "armature", "auto"))
+    return None if out is None else resolve_contacts(out, names, carriers)
 
 
 def validate(spec) -> None:
@@ -116,14 +124,33 @@ def validate(spec) -> None:
 class ContactInverseDynamics(ModelTensor):
     """The joint torques and contact wrenches of a wanted acceleration, from one env object's bound buffers (see the module docstring).  host:
     a DyrosDynamicWalk (TocabiAMPLower hands its physics host); vel_at_com: the host's root_vel_at_com unless given.  Buffers are allocated
-    here, once."""
+    here, once.  A subclass over another ABI of the same launch (stance_inverse_dynamics.py) gives NAME and the hooks below."""
 
     WHAT = "feature"
+    NAME = NAME
+
+    # ---- what differs between the ABIs ----
+    _declare = staticmethod(declare)
+
+    @staticmethod
+    def _resolve(spec, model):
+        return resolve(spec, model.body_names, model.body_moving)
+
+    def _pack(self, model):
+        """The packed table."""
+        return pack_table(self.api, model, self.ids, self.pos, self.weights)
+
+    def _extra(self, spec):
+        """The buffers beyond the common ones."""
+
+    def _arguments(self, accel, force_ref, outputs) -> tuple:
+        """The entry point's arguments after the gravity vector, in the ABI's order."""
+        return (accel, force_ref, self.vel_at_com) + outputs
 
     def __init__(self, host, spec=True, vel_at_com=None):
         model = host.model
-        spec = resolve(spec, model.body_names, model.body_moving)
-        super().__init__(host, spec, declare)
+        spec = self._resolve(spec, model)
+        super().__init__(host, spec, self._declare)
         N = self.num_envs
         self.ids, self.pos = list(spec["ids"]), [list(p) for p in spec["pos"]]
         self.names = [model.body_names[g] for g in self.ids]
@@ -134,8 +161,9 @@ class ContactInverseDynamics(ModelTensor):
         self.vel_at_com = self._vel_at_com(vel_at_com)
         self.g = tuple(float(x) for x in host.cfg["sim"].get("gravity", [0.0, 0.0, -9.81]))
         if len(self.g) != 3 or not all(math.isfinite(x) for x in self.g):
-            raise ValueError("contact_inverse_dynamics: sim.gravity must be three finite numbers")
-        self.table = self._upload(pack_table(self.api, model, self.ids, self.pos, self.weights))
+            raise ValueError("%s: sim.gravity must be three finite numbers" % self.NAME)
+        self._extra(spec)
+        self.table = self._upload(self._pack(model))
         self.accel = self._zeros(N, NV)
         self.force_ref = self._zeros(N, m)
         self.tau_joint = self._zeros(N, ND)
@@ -143,18 +171,18 @@ class ContactInverseDynamics(ModelTensor):
         self.force = self.force_all.view(N, self.num_contacts, 6)
         self.contact_accel = self._zeros(N, m) if spec["contact_accel"] else None
         self.tau_full = self._zeros(N, NV) if spec["tau_full"] else None
-        self._args = self._inputs(spec["armature"]) + self.g + (self.accel.data_ptr(), self.force_ref.data_ptr(), self.vel_at_com,
-                                                                self.tau_joint.data_ptr(), self.force_all.data_ptr(), ptr(self.contact_accel), ptr(self.tau_full))
+        self._args = self._inputs(spec["armature"]) + self.g + self._arguments(
+            self.accel.data_ptr(), self.force_ref.data_ptr(), (self.tau_joint.data_ptr(), self.force_all.data_ptr(), ptr(self.contact_accel), ptr(self.tau_full)))
 
     def index(self, name: str) -> int:
         """The contact (0 .. K - 1) on the body named."""
         if name not in self.names:
-            raise ValueError("contact_inverse_dynamics: no contact on %r (contacts: %s)" % (name, ", ".join(self.names)))
+            raise ValueError("%s: no contact on %r (contacts: %s)" % (self.NAME, name, ", ".join(self.names)))
         return self.names.index(name)
 
     def refresh(self):
-        """One launch on torch's current stream for `accel` and `force_ref` as they stand: `tau_joint`, `force`, and `contact_accel` and
-        `tau_full` where the spec holds them."""
+        """One launch on torch's current stream for the input buffers as they stand (`accel` and `force_ref`; under a stance also `stance`):
+        `tau_joint`, `force`, and the other outputs where the spec holds them."""
         self._launch("solve", self._args)
 
     def solve(self, accel=None, force_ref=None):

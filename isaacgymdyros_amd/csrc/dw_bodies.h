@@ -192,8 +192,9 @@ DWB_HD void com_finish(const float *acc, const float *root, float *com) {
 }
 
 // ---- host: the table from the model (dwb_pack_table) ----
-inline int pack(const DwbModel *M, uint32_t *t, char *err, size_t errn) {
-    auto fail = [&](const char *msg, int idx) { snprintf(err, errn, "dwb_pack_table: %s (index %d)", msg, idx); return -1; };
+// who: the entry point the refusals name (the tables of dw_jacobian.h and of what builds on it begin with this one)
+inline int pack(const DwbModel *M, uint32_t *t, char *err, size_t errn, const char *who = "dwb_pack_table") {
+    auto fail = [&](const char *msg, int idx) { snprintf(err, errn, "%s: %s (index %d)", who, msg, idx); return -1; };
     auto putf = [&](int k, double v) { const float f = (float)v; memcpy(t + k, &f, 4); };
     if (!M || !t) return fail("a pointer is missing", 0);
     memset(t, 0, sizeof(uint32_t) * DWB_TABLE_WORDS);

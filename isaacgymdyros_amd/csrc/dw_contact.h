@@ -112,14 +112,12 @@ DWB_HD float accel_word(const float *E, const float *x0, const float *f, int m, 
 DWB_HD float mirror_word(const float *W, int r, int c) { return r < c ? W[r * AS + c] : W[c * AS + r]; }
 
 // ---- host: the table from the model and the contacts (dwc_pack_table) ----
-inline int pack(const DwjModel *M, const DwcContacts *Cn, uint32_t *t, char *err, size_t errn) {
-    auto fail = [&](const char *msg, int idx) { snprintf(err, errn, "dwc_pack_table: %s (index %d)", msg, idx); return -1; };
+// who: the entry point the refusals name (dw_contact_inverse.h's and dw_stance_inverse.h's tables begin with this one)
+inline int pack(const DwjModel *M, const DwcContacts *Cn, uint32_t *t, char *err, size_t errn, const char *who = "dwc_pack_table") {
+    auto fail = [&](const char *msg, int idx) { snprintf(err, errn, "%s: %s (index %d)", who, msg, idx); return -1; };
     if (!M || !Cn || !t) return fail("a pointer is missing", 0);
     memset(t, 0, sizeof(uint32_t) * DWC_TABLE_WORDS);
-    if (dwl::pack(M, t, err, errn) != 0) {
-        if (errn > 2 && err[0] == 'd' && err[1] == 'w' && err[2] == 'l') err[2] = 'c';          // (the refusal is this entry point's)
-        return -1;
-    }
+    if (dwl::pack(M, t, err, errn, who) != 0) return -1;
     if (Cn->count < 1 || Cn->count > MAXK) return fail("count must be in 1..DWC_MAX_CONTACTS = 4", 0);
     t[DWC_T_K] = (uint32_t)Cn->count;
     for (int i = 0; i < Cn->count; ++i) {

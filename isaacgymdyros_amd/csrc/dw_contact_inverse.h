@@ -6,7 +6,9 @@
 // Y (the right side r[0:6] - J_b' f_ref, solved in place), F (the wrenches) and FR (f_ref, zeros when the caller has none).  CA (J_c a + Jd_c
 // nu) goes to the gravity row of dw_dynamics.h's OUT, which this launch never asks for.
 // Pieces: contact_point (PT and CA of one contact), jc_word, g_word, ldl_one / ldl_scale and sfwd_one / sscale_one / sback_one (dw_contact.h's
-// updates at G's stride), y_word, f_word, tauj_word.  pack() is the host's table builder.
+// updates at G's stride), y_word, f_word, tauj_word.  The sums over the rows go contact by contact over a `mask` of the contacts that carry
+// load, then over a contact's six rows: dwi_solve passes every contact, dwk_solve (dw_stance_inverse.h) each env's stance; with every
+// contact on these are the plain sums over r = 0 .. m - 1, term for term.  pack() is the host's table builder.
 #ifndef DW_CONTACT_INVERSE_H
 #define DW_CONTACT_INVERSE_H
 
@@ -58,11 +60,18 @@ DWB_HD float jc_word(const Tab &T, const float *E, int r, int c) {
     return dwj::jac_word(T, E, body(T, i) | ((E_PT + 3 * i) << 8), r - 6 * i, c);
 }
 
-// word u = 0 .. 20 of G's lower triangle, (i, j) with i >= j, row after row: the rows of J_b ascending
-DWB_HD void g_word(const Tab &T, float *E, int m, int u) {
+// the contacts that carry load as a mask, bit i for contact i; dwi_solve's is full(K)
+DWB_HD bool on(uint32_t mask, int i) { return ((mask >> i) & 1u) != 0u; }
+DWB_HD uint32_t full(int K) { return (1u << K) - 1u; }
+
+// word u = 0 .. 20 of G's lower triangle, (i, j) with i >= j, row after row: the rows of J_b of the active contacts, ascending
+DWB_HD void g_word(const Tab &T, float *E, int K, uint32_t mask, int u) {
     const int i = u < 1 ? 0 : (u < 3 ? 1 : (u < 6 ? 2 : (u < 10 ? 3 : (u < 15 ? 4 : 5)))), j = u - i * (i + 1) / 2;
     float v = 0.0f;
-    for (int r = 0; r < m; ++r) v += (jc_word(T, E, r, i) / weight(T, r)) * jc_word(T, E, r, j);
+    for (int c = 0; c < K; ++c) {
+        if (!on(mask, c)) continue;
+        for (int r = 6 * c; r < 6 * c + 6; ++r) v += (jc_word(T, E, r, i) / weight(T, r)) * jc_word(T, E, r, j);
+    }
     E[E_G + i * GS + j] = v;
     E[E_G + j * GS + i] = v;
 }
@@ -74,24 +83,32 @@ DWB_HD void sfwd_one(const float *G, float *g, int j, int i) { g[i] -= G[i * GS 
 DWB_HD void sscale_one(const float *G, float *g, int i) { g[i] = g[i] / G[i * GS + i]; }
 DWB_HD void sback_one(const float *G, float *g, int j, int i) { g[i] -= G[j * GS + i] * g[j]; }
 
-// word k of the right side of G y = r[0:6] - J_b' f_ref, in that order
-DWB_HD void y_word(const Tab &T, float *E, int m, int k) {
+// word k of the right side of G y = r[0:6] - J_b' f_ref, in that order, over the active rows
+DWB_HD void y_word(const Tab &T, float *E, int K, uint32_t mask, int k) {
     float s = 0.0f;
-    for (int r = 0; r < m; ++r) s += jc_word(T, E, r, k) * E[E_FR + r];
+    for (int c = 0; c < K; ++c) {
+        if (!on(mask, c)) continue;
+        for (int r = 6 * c; r < 6 * c + 6; ++r) s += jc_word(T, E, r, k) * E[E_FR + r];
+    }
     E[E_Y + k] = E[E_TAU + k] - s;
 }
 
-// word r of f = f_ref + W^-1 J_b y
-DWB_HD void f_word(const Tab &T, float *E, int r) {
+// word r of f = f_ref + W^-1 J_b y; +0.0 for a row of an inactive contact
+DWB_HD void f_word(const Tab &T, float *E, uint32_t mask, int r) {
+    if (!on(mask, r / 6)) {
+        E[E_F + r] = 0.0f;
+        return;
+    }
     float s = 0.0f;
     for (int k = 0; k < GN; ++k) s += jc_word(T, E, r, k) * E[E_Y + k];
     E[E_F + r] = E[E_FR + r] + s / weight(T, r);
 }
 
-// tau_joint[j] = r[6 + j] - J_j' f: the contacts that have joint j on their path, ascending
-DWB_HD float tauj_word(const Tab &T, const float *E, int K, int j) {
+// tau_joint[j] = r[6 + j] - J_j' f: the active contacts that have joint j on their path, ascending
+DWB_HD float tauj_word(const Tab &T, const float *E, int K, uint32_t mask, int j) {
     float s = 0.0f;
     for (int i = 0; i < K; ++i) {
+        if (!on(mask, i)) continue;
         const int b = body(T, i);
         if (!dwj::bit(T, DWJ_T_ANC, b, j + 1)) continue;
         for (int w = 0; w < 6; ++w) s += dwj::jac_word(T, E, b | ((E_PT + 3 * i) << 8), w, 6 + j) * E[E_F + 6 * i + w];
@@ -100,8 +117,8 @@ DWB_HD float tauj_word(const Tab &T, const float *E, int K, int j) {
 }
 
 // ---- host ----
-// one env's solve after g_word and y_word: the factor, the sweeps, f (the kernel spreads each step's updates over a wave)
-inline void solve_host(const Tab &T, float *E, int m) {
+// one env's factor and sweeps after g_word and y_word (the kernel spreads each step's updates over a wave)
+inline void factor_host(float *E) {
     float *G = E + E_G, *y = E + E_Y;
     for (int j = 0; j < GN - 1; ++j)
         for (int i = j + 1; i < GN; ++i)
@@ -113,19 +130,21 @@ inline void solve_host(const Tab &T, float *E, int m) {
     for (int i = 0; i < GN; ++i) sscale_one(G, y, i);
     for (int j = GN - 1; j >= 1; --j)
         for (int i = 0; i < j; ++i) sback_one(G, y, j, i);
-    for (int r = 0; r < m; ++r) f_word(T, E, r);
 }
 
-// the table from the model, the contacts and the weights (dwi_pack_table)
-inline int pack(const DwjModel *M, const DwcContacts *Cn, const float *weights, uint32_t *t, char *err, size_t errn) {
-    auto fail = [&](const char *msg, int idx) { snprintf(err, errn, "dwi_pack_table: %s (index %d)", msg, idx); return -1; };
+// one env's solve after g_word and y_word: an empty stance factors nothing; then f
+inline void solve_host(const Tab &T, float *E, int K, uint32_t mask) {
+    if (mask != 0u) factor_host(E);
+    for (int r = 0; r < 6 * K; ++r) f_word(T, E, mask, r);
+}
+
+// the table from the model, the contacts and the weights (dwi_pack_table); who: the entry point the refusals name
+inline int pack(const DwjModel *M, const DwcContacts *Cn, const float *weights, uint32_t *t, char *err, size_t errn, const char *who = "dwi_pack_table") {
+    auto fail = [&](const char *msg, int idx) { snprintf(err, errn, "%s: %s (index %d)", who, msg, idx); return -1; };
     if (!M || !Cn || !t) return fail("a pointer is missing", 0);
     memset(t, 0, sizeof(uint32_t) * DWI_TABLE_WORDS);
     uint32_t c[DWC_TABLE_WORDS];
-    if (dwc::pack(M, Cn, c, err, errn) != 0) {
-        if (errn > 2 && err[0] == 'd' && err[1] == 'w' && err[2] == 'c') err[2] = 'i';          // (the refusal is this entry point's)
-        return -1;
-    }
+    if (dwc::pack(M, Cn, c, err, errn, who) != 0) return -1;
     memcpy(t, c, sizeof(uint32_t) * DWI_T_K);          // (dwl_pack_table's table begins with dwj_pack_table's)
     memcpy(t + DWI_T_K, c + DWC_T_K, sizeof(uint32_t) * (1 + 4 * MAXK));
     const float one = 1.0f;

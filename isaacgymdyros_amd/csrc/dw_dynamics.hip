@@ -92,13 +92,7 @@ extern "C" {
 int dwn_abi_version(void) { return DWN_ABI_VERSION; }
 const char *dwn_last_error(void) { return s_err.s; }
 
-int dwn_pack_table(const DwjModel *m, uint32_t *table_host) {
-    if (dwj::pack(m, table_host, s_err.s, sizeof(s_err.s)) != 0) {
-        if (s_err.s[0] == 'd' && s_err.s[1] == 'w' && s_err.s[2] == 'j') s_err.s[2] = 'n';         // (the refusal is this entry point's)
-        return -1;
-    }
-    return 0;
-}
+int dwn_pack_table(const DwjModel *m, uint32_t *table_host) { return dwj::pack(m, table_host, s_err.s, sizeof(s_err.s), "dwn_pack_table"); }
 
 int dwn_inverse_dynamics(int32_t num_envs, const uint32_t *table, const float *root_states, const float *dof_state, const float *mass_scale,
                          const float *dof_armature, float gx, float gy, float gz, const float *accel, int32_t vel_at_com, float *bias,

@@ -97,13 +97,11 @@ DWB_HD bool minv_word(const float *W, int c0, int nc, int r, int c, float *out) 
 }
 
 // ---- host: the table from the model (dwl_pack_table) ----
-inline int pack(const DwjModel *M, uint32_t *t, char *err, size_t errn) {
-    if (!M || !t) { snprintf(err, errn, "dwl_pack_table: a pointer is missing (index 0)"); return -1; }
+// who: the entry point the refusals name
+inline int pack(const DwjModel *M, uint32_t *t, char *err, size_t errn, const char *who = "dwl_pack_table") {
+    if (!M || !t) { snprintf(err, errn, "%s: a pointer is missing (index 0)", who); return -1; }
     memset(t, 0, sizeof(uint32_t) * DWL_TABLE_WORDS);
-    if (dwj::pack(M, t, err, errn) != 0) {
-        if (errn > 2 && err[0] == 'd' && err[1] == 'w' && err[2] == 'j') err[2] = 'l';          // (the refusal is this entry point's)
-        return -1;
-    }
+    if (dwj::pack(M, t, err, errn, who) != 0) return -1;
     // dwb::pack has checked that parents precede children: a row's ancestors ascend from the base's side
     int p = 0;
     for (int r = 0; r < NV; ++r) {
@@ -116,12 +114,12 @@ inline int pack(const DwjModel *M, uint32_t *t, char *err, size_t errn) {
             while (na > 0) cols[n++] = 5 + anc[--na];
         }
         cols[n++] = r;
-        if (n > MAXROW) { snprintf(err, errn, "dwl_pack_table: a row of the pattern holds more than DWL_MAX_ROW words (index %d)", r); return -1; }
-        if (p + n > PAT) { snprintf(err, errn, "dwl_pack_table: the pattern holds more than DWL_PATTERN words (index %d)", r); return -1; }
+        if (n > MAXROW) { snprintf(err, errn, "%s: a row of the pattern holds more than DWL_MAX_ROW words (index %d)", who, r); return -1; }
+        if (p + n > PAT) { snprintf(err, errn, "%s: the pattern holds more than DWL_PATTERN words (index %d)", who, r); return -1; }
         for (int i = 0; i < n; ++i) t[DWL_T_COL + p++] = (uint32_t)((r << 8) | cols[i]);
     }
     t[DWL_T_ROW + NV] = (uint32_t)p;
-    if (p != PAT) { snprintf(err, errn, "dwl_pack_table: the pattern holds %d words, not DWL_PATTERN (index 0)", p); return -1; }
+    if (p != PAT) { snprintf(err, errn, "%s: the pattern holds %d words, not DWL_PATTERN (index 0)", who, p); return -1; }
     // the same words by columns, the diagonal left out
     int q = 0;
     for (int c = 0; c < NV; ++c) {

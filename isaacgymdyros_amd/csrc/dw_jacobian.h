@@ -199,8 +199,9 @@ DWB_HD float mm_word(const Tab &T, const float *E, const float *arm, int r, int 
 DWB_HD float cj_word(const Tab &T, const float *E, int r, int c) { return mm_word(T, E, nullptr, r, c) / E[E_BASE]; }
 
 // ---- host: the table from the model (dwj_pack_table) ----
-inline int pack(const DwjModel *M, uint32_t *t, char *err, size_t errn) {
-    auto fail = [&](const char *msg, int idx) { snprintf(err, errn, "dwj_pack_table: %s (index %d)", msg, idx); return -1; };
+// who: the entry point the refusals name
+inline int pack(const DwjModel *M, uint32_t *t, char *err, size_t errn, const char *who = "dwj_pack_table") {
+    auto fail = [&](const char *msg, int idx) { snprintf(err, errn, "%s: %s (index %d)", who, msg, idx); return -1; };
     if (!M || !t) return fail("a pointer is missing", 0);
     memset(t, 0, sizeof(uint32_t) * DWJ_TABLE_WORDS);
     DwbModel D;
@@ -213,10 +214,7 @@ inline int pack(const DwjModel *M, uint32_t *t, char *err, size_t errn) {
     memcpy(D.inert_mv, M->inert_mv, sizeof(D.inert_mv));
     memcpy(D.inert_mass, M->inert_mass, sizeof(D.inert_mass));
     memcpy(D.inert_com, M->inert_com, sizeof(D.inert_com));
-    if (dwb::pack(&D, t, err, errn) != 0) {
-        if (errn > 2 && err[0] == 'd' && err[1] == 'w' && err[2] == 'b') err[2] = 'j';          // (the refusal is this entry point's)
-        return -1;
-    }
+    if (dwb::pack(&D, t, err, errn, who) != 0) return -1;
     for (int k = 0; k < NI; ++k)
         for (int i = 0; i < 6; ++i) {
             if (!isfinite(M->inert_I[k][i])) return fail("inert_I is not finite", k);

@@ -1,7 +1,5 @@
-"""What the model-tensor features share on the host (DESIGN.md sections 21-28): the tables of the features -- FEATURES, the seven of sections
-21-27, and EXTENSIONS, the features built beside one of them (section 28's stance inverse dynamics beside section 27's contact inverse
-dynamics) -- by which the env classes and config.validate_cfg validate, attach and refresh them; the common front of their resolve(); and
-ModelTensor, the base of their classes.
+"""What the model-tensor features share on the host (DESIGN.md sections 21-28): the table of the features, FEATURES, by which the env classes
+and config.validate_cfg validate, attach and refresh them; the common front of their resolve(); and ModelTensor, the base of their classes.
 
 A feature is a module of this package with K, EXPORTS, DEFAULTS, declare, resolve and validate, and a class over one env object's bound
 buffers with `auto` and refresh().  DyrosDynamicWalk reads cfg sim.mi355.<name> and TocabiAMPLower sim.mi355.amp_<name> (its own keys: the
@@ -23,9 +21,6 @@ FEATURES = (
     ("forward_dynamics", "ForwardDynamics", ()),           # the solve of M nu_dot = rhs - h, the factor M = L' D L and M^-1
     ("contact_dynamics", "ContactDynamics", ()),           # the same under rigid contacts: J_c, the contact-space inertia, accelerations and forces
     ("contact_inverse_dynamics", "ContactInverseDynamics", ()),   # the inverse question: the joint torques and contact wrenches of a wanted acceleration
-)
-# rows of the same shape, walked after FEATURES
-EXTENSIONS = (
     ("stance_inverse_dynamics", "StanceInverseDynamics", ("terrain",)),   # the same per env's stance, with the soles' feasibility margins; plane only
 )
 
@@ -37,14 +32,14 @@ def _module(name):
 def validate_all(cfg: dict, prefix: str = "") -> None:
     """Every feature's validate() of cfg sim.mi355.<prefix><name>: ValueError before anything is loaded or allocated."""
     mi = cfg["sim"].get("mi355", {})
-    for name, _, extra in FEATURES + EXTENSIONS:
+    for name, _, extra in FEATURES:
         if mi.get(prefix + name) is not None:
             _module(name).validate(mi[prefix + name], *(cfg.get(k) for k in extra))
 
 
 def attach(env, host, mi355: dict, prefix: str = "") -> None:
     """env.<name> of every feature: its object over host's bound buffers where mi355[<prefix><name>] switches it on, None otherwise."""
-    for name, cls, _ in FEATURES + EXTENSIONS:
+    for name, cls, _ in FEATURES:
         spec = mi355.get(prefix + name)
         on = spec is not None and spec is not False          # (as validate reads it: {} is the default spec)
         f = getattr(_module(name), cls)(host, spec) if on else None
@@ -55,7 +50,7 @@ def attach(env, host, mi355: dict, prefix: str = "") -> None:
 
 def refresh_auto(env) -> None:
     """refresh() of every attached feature with "auto": True, in cfg order (after step(), reset_idx() and reset())."""
-    for name, _, _ in FEATURES + EXTENSIONS:
+    for name, _, _ in FEATURES:
         f = getattr(env, name)
         if f is not None and f.auto:
             f.refresh()

@@ -1,4 +1,4 @@
-"""The stance inverse dynamics (include/dyros_stance_inverse_dynamics.h, csrc/dw_stance_inverse.hip):
+"""The stance inverse dynamics (include/dyros_stance_inverse_dynamics.h, csrc/dw_contact_inverse.hip):
 contact_inverse_dynamics.py's question -- the joint torques and contact wrenches that give the robot a wanted acceleration, M a + h = [0;
 tau_joint] + J_c' f -- asked per env for the contacts that env stands on, with the distance of every loaded contact from what a sole can
 deliver.  A rollout holds envs in double support, in single support on either foot and in flight at once; `stance` [N, K] says which of the
@@ -42,10 +42,8 @@ import math
 import numpy as np
 
 from . import cbind
-from . import contact_dynamics as CM
 from . import contact_inverse_dynamics as IM
-from . import jacobians as JM
-from .model_tensors import ModelTensor, ptr, resolve_front
+from .model_tensors import ptr, resolve_front
 
 K = cbind.constants("dyros_stance_inverse_dynamics.h", "dwk_")
 EXPORTS = list(cbind.signatures("dyros_stance_inverse_dynamics.h", "dwk_"))
@@ -65,12 +63,7 @@ def pack_table(api: dict, model, ids, pos, weights=None, soles=None, mu=1.0) -> 
     """The device table's DWK_TABLE_WORDS words as a uint32 array (dwk_pack_table: dwi_pack_table's table, then the soles [K, 5] -- None:
     points at the contacts' pos -- and mu; raises for what it refuses)."""
     import ctypes as C
-    m, t = model if isinstance(model, JM.DwjModel) else JM.model_struct(model), np.zeros(TABLE_WORDS, np.uint32)
-    c = ids if isinstance(ids, CM.DwcContacts) else CM.contacts_struct(ids, pos)
-    n = max(1, min(c.count, MAX_CONTACTS))
-    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
-    if w is not None and w.size != 6 * n:
-        raise ValueError("%s: %d weights for %d contacts" % (NAME, w.size, c.count))
+    (m, c, w, n), t = IM.table_front(model, ids, pos, weights, NAME), np.zeros(TABLE_WORDS, np.uint32)
     s = None if soles is None else np.ascontiguousarray(np.asarray(soles, np.float32).reshape(-1))
     if s is not None and s.size != SOLE_WORDS * n:
         raise ValueError("%s: %d sole words for %d contacts" % (NAME, s.size, c.count))
@@ -133,11 +126,7 @@ def resolve(spec, model=None, terrain=None) -> dict:
     if dict(terrain or {}).get("mesh_type", "plane") in ("heightfield", "trimesh"):
         raise ValueError("%s: plane only -- the sole normal stands for the ground's (include/dyros_stance_inverse_dynamics.h)" % NAME)
     names, carriers = (None, None) if model is None else (model.body_names, model.body_moving)
-    try:
-        c = IM.resolve({"contacts": out["contacts"], "weights": out["weights"]}, names, carriers)
-    except ValueError as e:
-        raise ValueError(str(e).replace("contact_inverse_dynamics", NAME, 1)) from None
-    out["ids"], out["pos"], out["w"] = c["ids"], c["pos"], c["w"]
+    IM.resolve_contacts(out, names, carriers, NAME)
     mu = out["friction"]
     if not (isinstance(mu, (int, float, np.integer, np.floating)) and not isinstance(mu, bool) and math.isfinite(mu) and mu > 0):
         raise ValueError("%s.friction must be a finite positive number, not %r" % (NAME, mu))
@@ -157,75 +146,50 @@ def phase_stance(idx):
     return ~rssp, ~lssp
 
 
-class StanceInverseDynamics(ModelTensor):
+class StanceInverseDynamics(IM.ContactInverseDynamics):
     """The joint torques and contact wrenches of a wanted acceleration under each env's stance, with the soles' margins, from one env
     object's bound buffers (see the module docstring).  host: a DyrosDynamicWalk (TocabiAMPLower hands its physics host); vel_at_com: the
     host's root_vel_at_com unless given.  Buffers are allocated here, once."""
 
-    WHAT = "feature"
+    NAME = NAME
     task_host = True          # the host's task state is the env's (model_tensors.attach: False under TocabiAMPLower, whose host only carries the physics)
+    _declare = staticmethod(declare)
 
-    def __init__(self, host, spec=True, vel_at_com=None):
+    @staticmethod
+    def _resolve(spec, model):
+        return resolve(spec, model)
+
+    def _pack(self, model):
+        return pack_table(self.api, model, self.ids, self.pos, self.weights, self.soles, self.friction)
+
+    def _extra(self, spec):
         import torch
-        model = host.model
-        if getattr(host, "custom_origins", False):
-            raise ValueError("%s: plane only (include/dyros_stance_inverse_dynamics.h); this env runs on a height field" % NAME)
-        spec = resolve(spec, model)
-        super().__init__(host, spec, declare)
-        N = self.num_envs
-        self.ids, self.pos = list(spec["ids"]), [list(p) for p in spec["pos"]]
-        self.names = [model.body_names[g] for g in self.ids]
-        Kc = self.num_contacts = len(self.ids)
-        m = self.rows = 6 * Kc
-        self.weights = None if spec["w"] is None else list(spec["w"])
+        N, Kc = self.num_envs, self.num_contacts
         self.soles, self.friction = [list(s) for s in spec["sole_words"]], spec["friction"]
-        self.dof_names = list(model.dof_names)
-        self.vel_at_com = self._vel_at_com(vel_at_com)
-        self.g = tuple(float(x) for x in host.cfg["sim"].get("gravity", [0.0, 0.0, -9.81]))
-        if len(self.g) != 3 or not all(math.isfinite(x) for x in self.g):
-            raise ValueError("%s: sim.gravity must be three finite numbers" % NAME)
-        self.table = self._upload(pack_table(self.api, model, self.ids, self.pos, self.weights, self.soles, self.friction))
         self.stance = torch.ones(N, Kc, dtype=torch.uint8, device=self._tdev)
-        self.accel = self._zeros(N, NV)
-        self.force_ref = self._zeros(N, m)
-        self.tau_joint = self._zeros(N, ND)
-        self.force_all = self._zeros(N, m)
-        self.force = self.force_all.view(N, Kc, 6)
-        self.contact_accel = self._zeros(N, m) if spec["contact_accel"] else None
-        self.tau_full = self._zeros(N, NV) if spec["tau_full"] else None
         self.base_residual = self._zeros(N, 6) if spec["base_residual"] else None
         self.margins = self._zeros(N, Kc, MARGINS) if spec["margins"] else None
         self.feasible = torch.zeros(N, dtype=torch.uint8, device=self._tdev)
-        self._args = self._inputs(spec["armature"]) + self.g + (self.accel.data_ptr(), self.force_ref.data_ptr(), self.stance.data_ptr(), self.vel_at_com,
-                                                                self.tau_joint.data_ptr(), self.force_all.data_ptr(), ptr(self.contact_accel), ptr(self.tau_full),
-                                                                ptr(self.base_residual), ptr(self.margins), self.feasible.data_ptr())
+
+    def _arguments(self, accel, force_ref, outputs) -> tuple:
+        return (accel, force_ref, self.stance.data_ptr(), self.vel_at_com) + outputs + (ptr(self.base_residual), ptr(self.margins), self.feasible.data_ptr())
+
+    def __init__(self, host, spec=True, vel_at_com=None):
+        if getattr(host, "custom_origins", False):
+            raise ValueError("%s: plane only (include/dyros_stance_inverse_dynamics.h); this env runs on a height field" % NAME)
+        super().__init__(host, spec, vel_at_com)
         # the contacts on the two feet's moving bodies, for stance_from_phase
-        d = getattr(model, "d", model)
+        d = getattr(host.model, "d", host.model)
         feet = list(dict.fromkeys(f["moving"] for f in d["foot_pts"]))
         self._foot_contact = [next((i for i, g in enumerate(self.ids) if d["body_moving"][g] == mv), None) for mv in feet]          # (left, right)
         self._idx = self._forces = None
 
-    def index(self, name: str) -> int:
-        """The contact (0 .. K - 1) on the body named."""
-        if name not in self.names:
-            raise ValueError("%s: no contact on %r (contacts: %s)" % (NAME, name, ", ".join(self.names)))
-        return self.names.index(name)
-
-    def refresh(self):
-        """One launch on torch's current stream for `accel`, `force_ref` and `stance` as they stand."""
-        self._launch("solve", self._args)
-
     def solve(self, accel=None, force_ref=None, stance=None):
         """Copies accel [N, 39], force_ref [N, m] or [N, K, 6] and stance [N, K] into the buffers when given, one launch on torch's current
         stream; returns `tau_joint` [N, 33] and leaves the other outputs."""
-        if accel is not None:
-            self.accel.copy_(accel)
-        if force_ref is not None:
-            self.force_ref.copy_(force_ref.reshape(self.force_ref.shape))
         if stance is not None:
             self.stance.copy_(stance.reshape(self.stance.shape) != 0)
-        self._launch("solve", self._args)
-        return self.tau_joint
+        return super().solve(accel, force_ref)
 
     def stance_from_phase(self):
         """`stance` of the contacts on the left and the right foot from the env's mocap_data_idx (see the module docstring); returns

@@ -17,6 +17,7 @@ import body_states_ref as R
 import contact_dynamics_ref as CR
 import contact_inverse_dynamics_ref as IR
 import dynamics_ref as DR
+import inverse_dynamics_resources as RES
 from isaacgymdyros_amd import build, cbind
 from isaacgymdyros_amd import contact_dynamics as CM
 from isaacgymdyros_amd import contact_inverse_dynamics as IM
@@ -103,7 +104,7 @@ def host(tmp_path_factory):
     for out, src in ((so, "contact_inverse_dynamics_host.cpp"), (so_n, "dynamics_host.cpp")):
         subprocess.check_call([gxx, "-O2", "-std=c++17", "-shared", "-fPIC", "-ffp-contract=off", "-o", out, os.path.join(ROOT, "tests", src)])
     lib = C.CDLL(so)
-    lib.dwih_solve.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_float] * 3 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 4
+    lib.dwih_solve.argtypes = lib.dwih_solve_product.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_float] * 3 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 4
     lib.dwih_pack_table.argtypes = [C.POINTER(JM.DwjModel), C.POINTER(CM.DwcContacts), C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
     lib.model = JM.model_struct(load_model())
     lib.tables = {}
@@ -127,12 +128,13 @@ def host_table(lib, contacts, weights=None):
     return lib.tables[key]
 
 
-def host_run(lib, contacts, root, dof, ms, arm, vel_at_com, accel=None, f_ref=None, weights=None, outs=OUTS, g=GRAV, expect=0):
-    """The outputs named, NaN-filled beforehand, as a dict (the others None)."""
+def host_run(lib, contacts, root, dof, ms, arm, vel_at_com, accel=None, f_ref=None, weights=None, outs=OUTS, g=GRAV, expect=0, fn="dwih_solve"):
+    """The outputs named, NaN-filled beforehand, as a dict (the others None).  fn: dwih_solve, section 27's plain row-ordered sums, stated in
+    the host file only; or dwih_solve_product, the sums dwi_solve runs (contact by contact, every contact on)."""
     n, m = len(root), 6 * len(contacts)
     shape = {"tau_joint": (n, 33), "force": (n, m), "contact_accel": (n, m), "tau_full": (n, 39)}
     o = {k: np.full(shape[k], np.nan, F) if k in outs else None for k in OUTS}
-    rc = lib.dwih_solve(n, _p(host_table(lib, contacts, weights)), _p(root), _p(dof), _p(ms), _p(arm), g[0], g[1], g[2], _p(accel), _p(f_ref), vel_at_com,
+    rc = getattr(lib, fn)(n, _p(host_table(lib, contacts, weights)), _p(root), _p(dof), _p(ms), _p(arm), g[0], g[1], g[2], _p(accel), _p(f_ref), vel_at_com,
                         *[_p(o[k]) for k in OUTS])
     assert rc == expect
     return o
@@ -235,6 +237,18 @@ def test_exact_properties(host, vel_at_com):
         assert (res <= allow).all()
 
 
+@pytest.mark.parametrize("vel_at_com", [0, 1])
+@pytest.mark.parametrize("K", [1, 2, 4])
+def test_product_sums_are_the_plain_row_ordered_sums(host, K, vel_at_com):
+    """The sums dwi_solve runs -- contact by contact over the full mask, then a contact's six rows -- against section 27's plain statement, r =
+    0 .. m - 1 with the contact r / 6: the same bits in all four outputs, moments weighted 10 x, with f_ref."""
+    root, dof, ms, arm, acc = DR.seeded(N, 23)
+    fr = IR.fref_of(N, 6 * K, 25)
+    plain = host_run(host, IR.SETS[K], root, dof, ms, arm, vel_at_com, acc, fr, IR.MOMENTS_10)
+    product = host_run(host, IR.SETS[K], root, dof, ms, arm, vel_at_com, acc, fr, IR.MOMENTS_10, fn="dwih_solve_product")
+    assert all(np.isfinite(plain[k]).all() and same(product[k], plain[k]) for k in OUTS)
+
+
 def test_non_finite_inputs_stay_in_their_env(host):
     cs = IR.SETS[2]
     root, dof, ms, arm, acc = DR.seeded(6, 41)
@@ -289,8 +303,7 @@ def test_header_python_and_library_agree(check, tmp_path):
     assert K["DWI_TABLE_WORDS"] == K["DWI_T_W"] + 24 + 3 and K["DWI_TABLE_WORDS"] % 4 == 0
     assert IM.DEFAULTS == {"contacts": [{"body": "L_Foot_Link", "pos": [0.0, 0.0, -0.09]}, {"body": "R_Foot_Link", "pos": [0.0, 0.0, -0.09]}], "weights": None,
                            "contact_accel": True, "tau_full": False, "armature": True, "auto": False}
-    from isaacgymdyros_amd import model_tensors as MT
-    assert MT.FEATURES[-1][:2] == ("contact_inverse_dynamics", "ContactInverseDynamics") and len(MT.FEATURES) == 7
+    # (model_tensors.FEATURES is pinned whole, this feature's row included, in tests/test_stance_inverse_dynamics.py)
     # the older headers are untouched
     assert KC["DWC_ABI_VERSION"] == 1 and KN["DWN_ABI_VERSION"] == 1 and JM.K["DWJ_ABI_VERSION"] == 1
 
@@ -366,28 +379,15 @@ def test_refusals_happen_before_any_launch(api):
 
 
 # ---------------------------------------------------------------------------------------------- 6. the kernel's resources
-def _remarks(src):
-    extra = dict(build.SOURCES)[src]
-    cmd = [build.hipcc()] + build.FLAGS + extra + ["-Rpass-analysis=kernel-resource-usage", "-c", "-o", os.devnull, os.path.join(build.CSRC, src)]
-    return subprocess.run(cmd, cwd=build.CSRC, capture_output=True, text=True, check=True).stderr
-
-
 def test_kernel_uses_no_scratch_and_keeps_dwn_residency():
-    """One kernel, no scratch; its LDS is no more than dwn_k_inverse_dynamics's group plus the tail (the table's 44 further words, and per env
-    the points 12, G 6 x 7, y 6, f 24 and f_ref 24 = 108 words), and four workgroups -- 16 envs -- still share a CU's 160 KB."""
-    remarks, dwn = _remarks(SRC), _remarks("dw_dynamics.hip")
-    names = re.findall(r"remark: Function Name: (\S+)", remarks)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", remarks)]
-    lds = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", remarks)]
-    occ = [int(x) for x in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", remarks)]
-    lds_n = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", dwn)]
-    occ_n = [int(x) for x in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", dwn)]
-    assert len(names) == 1 and len(scratch) == len(lds) == len(occ) == 1 and len(lds_n) == len(occ_n) == 1
-    n = names[0]
-    assert "dwi_k_solve" in n and scratch[0] == 0
+    """Exactly two kernels in the unit, dwi_k_solve and dwk_k_solve; dwi_k_solve: no scratch; its LDS is no more than
+    dwn_k_inverse_dynamics's group plus the tail (the table's 44 further words, and per env the points 12, G 6 x 7, y 6, f 24 and f_ref 24 =
+    108 words), and four workgroups -- 16 envs -- still share a CU's 160 KB."""
+    (n, r), _dwk, rn = RES.solve_kernels()
+    assert r["scratch"] == 0
     tail = 4 * ((IM.K["DWI_TABLE_WORDS"] - IM.K["DWI_T_K"]) + IM.GROUP * (12 + 6 * 7 + 6 + 24 + 24))
-    print("dwi_k_solve: LDS %d bytes per workgroup (dwn %d, the tail %d), %d waves per SIMD (dwn %d)" % (lds[0], lds_n[0], tail, occ[0], occ_n[0]))
-    assert lds[0] <= lds_n[0] + tail and lds[0] <= 160 * 1024 // 4 and occ[0] >= occ_n[0]
+    print("dwi_k_solve: %d VGPRs, LDS %d bytes per workgroup (dwn %d, the tail %d), %d waves per SIMD (dwn %d)" % (r["vgprs"], r["lds"], rn["lds"], tail, r["occ"], rn["occ"]))
+    assert r["lds"] <= rn["lds"] + tail and r["lds"] <= 160 * 1024 // 4 and r["occ"] >= rn["occ"]
     assert not any(x in n for x in tuple(TAKEN) + tuple(TAKEN_BODIES) + ("dwg_k_", "dwb_k_", "dwf_k_", "dwj_k_", "dwn_k_", "dwl_k_", "dwc_k_")), n
     assert not any(x in n for x in ("k_mlp", "k_wgrad", "k_policy", "k_adam", "k_grad_stats", "k_finish", "k_gae", "k_roll_pre", "k_roll_post", "k_loss",
                                     "k_relu_bwd", "k_bias_relu", "k_stage_obs", "k_retile", "dw_k_amp", "dw_k_newwalk", "dw_k_body_positions")), n

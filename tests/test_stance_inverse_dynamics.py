@@ -1,8 +1,9 @@
 """The stance inverse dynamics without a GPU (include/dyros_stance_inverse_dynamics.h, isaacgymdyros_amd/csrc/dw_stance_inverse.h, DESIGN.md
 section 28): the reference (tests/stance_inverse_dynamics_ref.py) against what it is not itself -- section 27's reference on the contact
-subset; the per-env arithmetic -- compiled by g++ from the headers the HIP kernel includes (tests/stance_inverse_dynamics_host.cpp) -- against
-the float64 reference under its measured tolerance; the exact properties against a g++ build of section 27's arithmetic; the standing pose;
-stance_from_phase's windows; the header, the Python binding and the built library; refusals; the kernel's resources; the cfg surface."""
+subset; the per-env arithmetic -- compiled by g++ from the headers the HIP kernel includes (tests/contact_inverse_dynamics_host.cpp) -- against
+the float64 reference under its measured tolerance; the exact properties against section 27's plain row-ordered sums, stated in that g++
+build only; the standing pose; stance_from_phase's windows; the header, the Python binding and the built library; refusals; the kernel's
+resources; the cfg surface."""
 import ctypes as C
 import os
 import re
@@ -15,6 +16,7 @@ import pytest
 import contact_dynamics_ref as CR
 import contact_inverse_dynamics_ref as IR
 import dynamics_ref as DR
+import inverse_dynamics_resources as RES
 import stance_inverse_dynamics_ref as SR
 from isaacgymdyros_amd import build, cbind
 from isaacgymdyros_amd import contact_dynamics as CM
@@ -24,7 +26,7 @@ from isaacgymdyros_amd import stance_inverse_dynamics as SM
 from isaacgymdyros_amd.model import load_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = "dw_stance_inverse.hip"
+SRC = "dw_contact_inverse.hip"          # (one unit holds dwi_k_solve and dwk_k_solve)
 HEADER = "dyros_stance_inverse_dynamics.h"
 N = 37
 F, U = np.float32, np.uint32
@@ -86,17 +88,15 @@ def test_reference_is_section_27s_on_the_contact_subset(K, vel_at_com):
 def host(tmp_path_factory):
     gxx = shutil.which("g++")
     if gxx is None:
-        pytest.fail("g++ is needed to build tests/stance_inverse_dynamics_host.cpp")
-    d = tmp_path_factory.mktemp("dwkh")
-    so, so_i = str(d / "libdwkh.so"), str(d / "libdwih.so")
-    for out, src in ((so, "stance_inverse_dynamics_host.cpp"), (so_i, "contact_inverse_dynamics_host.cpp")):
-        subprocess.check_call([gxx, "-O2", "-std=c++17", "-shared", "-fPIC", "-ffp-contract=off", "-o", out, os.path.join(ROOT, "tests", src)])
+        pytest.fail("g++ is needed to build tests/contact_inverse_dynamics_host.cpp")
+    so = str(tmp_path_factory.mktemp("dwkh") / "libdwkh.so")
+    subprocess.check_call([gxx, "-O2", "-std=c++17", "-shared", "-fPIC", "-ffp-contract=off", "-o", so, os.path.join(ROOT, "tests", "contact_inverse_dynamics_host.cpp")])
     lib = C.CDLL(so)
     lib.dwkh_solve.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_float] * 3 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 7
     lib.dwkh_pack_table.argtypes = [C.POINTER(JM.DwjModel), C.POINTER(CM.DwcContacts), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_char_p, C.c_int]
     lib.model = JM.model_struct(load_model())
     lib.tables = {}
-    lib.inv = C.CDLL(so_i)
+    lib.inv = lib          # (dwih_solve: section 27's plain row-ordered sums, stated in the host file only)
     lib.inv.dwih_solve.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_float] * 3 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 4
     lib.inv.dwih_pack_table.argtypes = [C.POINTER(JM.DwjModel), C.POINTER(CM.DwcContacts), C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
     return lib
@@ -133,7 +133,7 @@ def host_run(lib, contacts, root, dof, ms, arm, vel_at_com, stance=None, accel=N
 
 
 def inv_run(lib, contacts, root, dof, ms, arm, vel_at_com, accel=None, f_ref=None, weights=None, g=GRAV):
-    """The g++ build of section 27's arithmetic (tests/contact_inverse_dynamics_host.cpp)."""
+    """The g++ build of section 27's plain row-ordered arithmetic (tests/contact_inverse_dynamics_host.cpp's dwih_solve)."""
     n, m = len(root), 6 * len(contacts)
     table, err = np.zeros(IM.TABLE_WORDS, U), C.create_string_buffer(256)
     st = CM.contacts_struct(CR.ids_of(contacts), [p for _, p in contacts])
@@ -312,8 +312,11 @@ def test_header_python_and_library_agree(check, tmp_path):
     assert SM.DEFAULTS == {"contacts": IM.DEFAULTS["contacts"], "weights": None, "soles": "model", "friction": 1.0, "contact_accel": True, "margins": True,
                            "base_residual": True, "tau_full": False, "armature": True, "auto": False}
     from isaacgymdyros_amd import model_tensors as MT
-    assert len(MT.FEATURES) == 7 and MT.FEATURES[-1][:2] == ("contact_inverse_dynamics", "ContactInverseDynamics")
-    assert MT.EXTENSIONS == (("stance_inverse_dynamics", "StanceInverseDynamics", ("terrain",)),)
+    # the whole table of the model-tensor features, in cfg order: one table, no second one beside it
+    assert MT.FEATURES == (("body_states", "BodyStates", ()), ("force_sensors", "ForceSensors", ("terrain",)), ("jacobians", "Jacobians", ()),
+                           ("dynamics", "Dynamics", ()), ("forward_dynamics", "ForwardDynamics", ()), ("contact_dynamics", "ContactDynamics", ()),
+                           ("contact_inverse_dynamics", "ContactInverseDynamics", ()), ("stance_inverse_dynamics", "StanceInverseDynamics", ("terrain",)))
+    assert not hasattr(MT, "EXTENSIONS")
     # section 27's header is untouched
     assert KI["DWI_ABI_VERSION"] == 1 and sorted(IM.EXPORTS) == ["abi_version", "last_error", "pack_table", "solve"]
 
@@ -399,28 +402,14 @@ def test_refusals_happen_before_any_launch(api):
 
 
 # ---------------------------------------------------------------------------------------------- 8. the kernel's resources
-def _remarks(src):
-    extra = dict(build.SOURCES)[src]
-    cmd = [build.hipcc()] + build.FLAGS + extra + ["-Rpass-analysis=kernel-resource-usage", "-c", "-o", os.devnull, os.path.join(build.CSRC, src)]
-    return subprocess.run(cmd, cwd=build.CSRC, capture_output=True, text=True, check=True).stderr
-
-
 def test_kernel_uses_no_scratch_and_keeps_dwn_residency():
-    """One kernel in the unit, no scratch, LDS <= 40 960 B (four workgroups -- 16 envs -- share a CU's 160 KB), occupancy no lower than
-    dwn_k_inverse_dynamics's; section 27's unit still holds its one kernel."""
-    remarks, dwn, dwi = _remarks(SRC), _remarks("dw_dynamics.hip"), _remarks("dw_contact_inverse.hip")
-    names = re.findall(r"remark: Function Name: (\S+)", remarks)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", remarks)]
-    lds = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", remarks)]
-    occ = [int(x) for x in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", remarks)]
-    occ_n = [int(x) for x in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", dwn)]
-    lds_i = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", dwi)]
-    assert len(names) == 1 and len(scratch) == len(lds) == len(occ) == 1 and len(occ_n) == 1 and len(lds_i) == 1
-    assert "dwk_k_solve" in names[0] and scratch[0] == 0
-    print("dwk_k_solve: LDS %d bytes per workgroup (dwi %d), %d waves per SIMD (dwn %d)" % (lds[0], lds_i[0], occ[0], occ_n[0]))
+    """Exactly two kernels in the unit, dwi_k_solve and dwk_k_solve; dwk_k_solve: no scratch, LDS <= 40 960 B (four workgroups -- 16 envs --
+    share a CU's 160 KB), occupancy no lower than dwn_k_inverse_dynamics's."""
+    (_n, ri), (_nk, r), rn = RES.solve_kernels()
+    assert r["scratch"] == 0
+    print("dwk_k_solve: %d VGPRs, LDS %d bytes per workgroup (dwi %d), %d waves per SIMD (dwn %d)" % (r["vgprs"], r["lds"], ri["lds"], r["occ"], rn["occ"]))
     # dwi_k_solve's store, the table's 24 further words and a mask word per env
-    assert lds[0] <= lds_i[0] + 4 * (SM.TABLE_WORDS - IM.TABLE_WORDS + SM.GROUP) and lds[0] <= 40960 and occ[0] >= occ_n[0]
-    assert len(re.findall(r"remark: Function Name: (\S+)", dwi)) == 1
+    assert r["lds"] <= ri["lds"] + 4 * (SM.TABLE_WORDS - IM.TABLE_WORDS + SM.GROUP) and r["lds"] <= 40960 and r["occ"] >= rn["occ"]
 
 
 # ---------------------------------------------------------------------------------------------- 9. the Python surface

@@ -1,4 +1,4 @@
-"""The stance inverse dynamics on an MI355X (include/dyros_stance_inverse_dynamics.h, csrc/dw_stance_inverse.hip): the HIP
+"""The stance inverse dynamics on an MI355X (include/dyros_stance_inverse_dynamics.h, csrc/dw_contact_inverse.hip): the HIP
 kernel against the float64 reference of tests/stance_inverse_dynamics_ref.py under its measured tolerance at the workgroup's edges, with the
 four envs of a workgroup in four different stances (flight among them), the output buffers filled with NaN, too long, and their tails
 watched; the exact properties against dwi_solve on the device; the ways to choose outputs; a misaligned table; a live env with resets and
