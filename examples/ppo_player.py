@@ -44,6 +44,9 @@ each played state; without the flag the files are unchanged.
 With --dynamics-stance it turns the stance inverse dynamics on (isaacgymdyros_amd/stance_inverse_dynamics.py) and adds
 stance [T, 2] (which foot the gait's phase loads), stance_torque [T, 33], stance_force [T, 2, 6] and stance_margins [T, 2, 4]: the same
 question under the phase's stance, and how far each loaded sole is from what it can deliver; without the flag the files are unchanged.
+With --dynamics-ik it turns the inverse kinematics on (isaacgymdyros_amd/inverse_kinematics.py) and, at each played step,
+solves both feet's played poses from the model's initial joint angles; it adds ik_q [T, 33], ik_err [T, 2] (the largest position and
+orientation error left) and ik_converged [T]; without the flag the files are unchanged.
 """
 from __future__ import annotations
 
@@ -108,6 +111,8 @@ def run(args):
             cfg["sim"]["mi355"]["contact_inverse_dynamics"] = {"contact_accel": False, "auto": True}
         if args.dynamics_stance:
             cfg["sim"]["mi355"]["stance_inverse_dynamics"] = {"contact_accel": False, "base_residual": False}
+        if args.dynamics_ik:
+            cfg["sim"]["mi355"]["inverse_kinematics"] = True
         os.makedirs(args.dynamics_dir, exist_ok=True)
     env = DyrosDynamicWalk(cfg, args.device, 0, True)
     traces_written = 0
@@ -149,6 +154,11 @@ def run(args):
         rec_stt = torch.zeros(args.max_steps, dynamics_k, 33, device=dev)
         rec_stf = torch.zeros(args.max_steps, dynamics_k, 2, 6, device=dev)
         rec_stm = torch.zeros(args.max_steps, dynamics_k, 2, 4, device=dev)
+    ik = bool(dynamics_k and args.dynamics_ik)
+    if ik:
+        rec_ikq = torch.zeros(args.max_steps, dynamics_k, 33, device=dev)
+        rec_ike = torch.zeros(args.max_steps, dynamics_k, 2, device=dev)
+        rec_ikc = torch.zeros(args.max_steps, dynamics_k, dtype=torch.uint8, device=dev)
     played = 0
     ck = PK.load(args.checkpoint)
     n_obs, n_act = int(ck["model"][PK.PREFIX + "actor_mlp.0.weight"].shape[1]), int(ck["model"][PK.PREFIX + "mu.weight"].shape[0])
@@ -200,6 +210,13 @@ def run(args):
             rec_stt[_n].copy_(sd.tau_joint[:dynamics_k])
             rec_stf[_n].copy_(sd.force[:dynamics_k])
             rec_stm[_n].copy_(sd.margins[:dynamics_k])
+        if ik:               # (the feet where the policy put them, the joints from where the model starts)
+            qk = env.inverse_kinematics
+            qk.targets_from_bodies()
+            qk.solve(q0=env.initial_dof_pos)
+            rec_ikq[_n].copy_(qk.q[:dynamics_k])
+            rec_ike[_n].copy_(qk.err[:dynamics_k])
+            rec_ikc[_n].copy_(qk.converged[:dynamics_k])
         played = _n + 1
         cr += r.view(N)
         steps += 1
@@ -265,6 +282,8 @@ def run(args):
             if stance:
                 more.update(stance=rec_st[:played, e].cpu().numpy(), stance_torque=rec_stt[:played, e].cpu().numpy(),
                             stance_force=rec_stf[:played, e].cpu().numpy(), stance_margins=rec_stm[:played, e].cpu().numpy())
+            if ik:
+                more.update(ik_q=rec_ikq[:played, e].cpu().numpy(), ik_err=rec_ike[:played, e].cpu().numpy(), ik_converged=rec_ikc[:played, e].cpu().numpy())
             np.savez(os.path.join(args.dynamics_dir, "dynamics_env%d.npz" % e), names=np.asarray(jc.names), dof_names=np.asarray(jc.dof_names),
                      dt=np.float64(jc.dt), jacobian=rec_jac[:played, e].cpu().numpy(), mass_matrix=rec_mm[:played, e].cpu().numpy(),
                      com_jacobian=rec_cj[:played, e].cpu().numpy(), **more)
@@ -308,6 +327,7 @@ def main():
     ap.add_argument("--dynamics-contact", action="store_true", help="with --dynamics-dir: add the feet's contact Jacobian, the contact-space inertia and the zero-torque ground reaction with planted feet to each file")
     ap.add_argument("--dynamics-inverse", action="store_true", help="with --dynamics-dir: add the joint torques and foot wrenches that would hold nu_dot = 0 at each played state to each file")
     ap.add_argument("--dynamics-stance", action="store_true", help="with --dynamics-dir: add the stance of the gait's phase, and the joint torques, foot wrenches and sole margins that would hold nu_dot = 0 under it, to each file")
+    ap.add_argument("--dynamics-ik", action="store_true", help="with --dynamics-dir: add the joint angles that put both feet at their played poses, solved from the model's initial angles, to each file")
     ap.add_argument("--dynamics-forces", action="store_true", help="with --dynamics-dir: add the bias forces, the gravity forces and the momentum to each file")
     ap.add_argument("--device", default="cuda:0")
     run(ap.parse_args())

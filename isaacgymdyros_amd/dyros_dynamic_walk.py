@@ -118,8 +118,8 @@ class DyrosDynamicWalk(VecTask):
         if spec is not None and spec is not False:
             from .gait_profile import GaitProfile
             self.gait_profile = GaitProfile(self, spec)
-        # cfg sim.mi355.body_states, force_sensors, jacobians, dynamics, forward_dynamics, contact_dynamics, contact_inverse_dynamics, stance_inverse_dynamics: the model tensors, one launch per
-        # refresh or call (isaacgymdyros_amd/model_tensors.py's tables, DESIGN.md sections 21-28); off: None, no buffer, and step() makes no
+        # cfg sim.mi355.body_states, force_sensors, jacobians, dynamics, forward_dynamics, contact_dynamics, contact_inverse_dynamics, stance_inverse_dynamics, inverse_kinematics: the model tensors, one launch per
+        # refresh or call (isaacgymdyros_amd/model_tensors.py's tables, DESIGN.md sections 21-29); off: None, no buffer, and step() makes no
         # extra launch
         model_tensors.attach(self, self, self.cfg["sim"].get("mi355", {}))
 

@@ -1,4 +1,4 @@
-"""What the model-tensor features share on the host (DESIGN.md sections 21-28): the table of the features, FEATURES, by which the env classes
+"""What the model-tensor features share on the host (DESIGN.md sections 21-29): the tables of the features, FEATURES and SOLVERS, by which the env classes
 and config.validate_cfg validate, attach and refresh them; the common front of their resolve(); and ModelTensor, the base of their classes.
 
 A feature is a module of this package with K, EXPORTS, DEFAULTS, declare, resolve and validate, and a class over one env object's bound
@@ -23,6 +23,11 @@ FEATURES = (
     ("contact_inverse_dynamics", "ContactInverseDynamics", ()),   # the inverse question: the joint torques and contact wrenches of a wanted acceleration
     ("stance_inverse_dynamics", "StanceInverseDynamics", ("terrain",)),   # the same per env's stance, with the soles' feasibility margins; plane only
 )
+# FEATURES holds the tensors of the state the simulator is in.  SOLVERS holds what asks the opposite question -- which state would do -- and is
+# walked after it: validated, attached and refreshed the same way, under the same keys
+SOLVERS = (
+    ("inverse_kinematics", "InverseKinematics", ()),       # the joint angles (and base pose) that put bodies at wanted poses [N, 33]
+)
 
 
 def _module(name):
@@ -32,14 +37,14 @@ def _module(name):
 def validate_all(cfg: dict, prefix: str = "") -> None:
     """Every feature's validate() of cfg sim.mi355.<prefix><name>: ValueError before anything is loaded or allocated."""
     mi = cfg["sim"].get("mi355", {})
-    for name, _, extra in FEATURES:
+    for name, _, extra in FEATURES + SOLVERS:
         if mi.get(prefix + name) is not None:
             _module(name).validate(mi[prefix + name], *(cfg.get(k) for k in extra))
 
 
 def attach(env, host, mi355: dict, prefix: str = "") -> None:
     """env.<name> of every feature: its object over host's bound buffers where mi355[<prefix><name>] switches it on, None otherwise."""
-    for name, cls, _ in FEATURES:
+    for name, cls, _ in FEATURES + SOLVERS:
         spec = mi355.get(prefix + name)
         on = spec is not None and spec is not False          # (as validate reads it: {} is the default spec)
         f = getattr(_module(name), cls)(host, spec) if on else None
@@ -50,7 +55,7 @@ def attach(env, host, mi355: dict, prefix: str = "") -> None:
 
 def refresh_auto(env) -> None:
     """refresh() of every attached feature with "auto": True, in cfg order (after step(), reset_idx() and reset())."""
-    for name, _, _ in FEATURES:
+    for name, _, _ in FEATURES + SOLVERS:
         f = getattr(env, name)
         if f is not None and f.auto:
             f.refresh()

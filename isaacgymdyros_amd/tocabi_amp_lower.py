@@ -175,8 +175,8 @@ class TocabiAMPLower(VecTask):
         self._amp_stats_on = cfg["sim"].get("mi355", {}).get("amp_episode_stats", False)
         if not isinstance(self._amp_stats_on, bool):
             raise ValueError("sim.mi355.amp_episode_stats must be True or False")
-        # cfg sim.mi355.amp_body_states, amp_force_sensors, amp_jacobians, amp_dynamics, amp_forward_dynamics, amp_contact_dynamics, amp_contact_inverse_dynamics, amp_stance_inverse_dynamics: the model
-        # tensors over the physics host's bound buffers (isaacgymdyros_amd/model_tensors.py's tables, DESIGN.md sections 21-28); off: None.
+        # cfg sim.mi355.amp_body_states, amp_force_sensors, amp_jacobians, amp_dynamics, amp_forward_dynamics, amp_contact_dynamics, amp_contact_inverse_dynamics, amp_stance_inverse_dynamics, amp_inverse_kinematics: the model
+        # tensors over the physics host's bound buffers (isaacgymdyros_amd/model_tensors.py's tables, DESIGN.md sections 21-29); off: None.
         # This class' own keys for the same reason: the plain ones would reach the physics host
         model_tensors.validate_all(cfg, "amp_")
         e["numObservations"] = (NUM_OBS + NUM_ACTIONS) * self.num_obs_his - NUM_ACTIONS            # :83
@@ -190,7 +190,7 @@ class TocabiAMPLower(VecTask):
         # (physx.num_position_iterations + num_velocity_iterations = the contact solver's iteration count, as the task yaml gives them:
         #  4 + 0 for this task, cfg/task/TocabiAMPLower.yaml)
         # (this class' own keys stay here, spelled out: tests/test_forward_dynamics.py and tests/test_contact_dynamics.py read them in this text)
-        pc["sim"]["mi355"].update({k: v for k, v in cfg["sim"].get("mi355", {}).items() if k not in ("amp_episode_stats", "amp_body_states", "amp_force_sensors", "amp_jacobians", "amp_dynamics", "amp_forward_dynamics", "amp_contact_dynamics", "amp_contact_inverse_dynamics", "amp_stance_inverse_dynamics")})
+        pc["sim"]["mi355"].update({k: v for k, v in cfg["sim"].get("mi355", {}).items() if k not in ("amp_episode_stats", "amp_body_states", "amp_force_sensors", "amp_jacobians", "amp_dynamics", "amp_forward_dynamics", "amp_contact_dynamics", "amp_contact_inverse_dynamics", "amp_stance_inverse_dynamics", "amp_inverse_kinematics")})
         pc["env"]["perturbation"] = False
         # spawn height: the reference's 0.89 (:394) puts the soles 2.2 cm INTO the plane in the initial pose; PhysX resolves that
         # positionally, this simulator's contact model through a velocity bias (erp), which launches the robot at 2 m/s.  Default
