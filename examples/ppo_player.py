@@ -28,6 +28,10 @@ quaternion xyzw, linear and angular velocity of every body in the world frame) a
 0 .. --sensors-envs - 1 at every step; at the end it writes DIR/sensors_env<id>.npz with names, dt, sensors [T, S, 6] (force then torque of the
 ground on each foot, in the sensor frame), cop [T, 2, 4] (x, y in the foot frame, Fz, loaded corners) and zmp [T, 4].
 
+--scan-dir DIR turns the terrain height scan on (isaacgymdyros_amd/height_scan.py) and records envs
+0 .. --scan-envs - 1 at every step; at the end it writes DIR/scan_env<id>.npz with grid [P, 2], names, dt, heights [T, P] (the ground around
+the base, the reference's get_heights), probe_pos [T, B, 3] and clearance [T, B] (the sole corners and their height over the ground).
+
 --dynamics-dir DIR turns the Jacobian and mass-matrix tensors on (isaacgymdyros_amd/jacobians.py) and records envs
 0 .. --dynamics-envs - 1 at every step; at the end it writes DIR/dynamics_env<id>.npz with names, dof_names, dt, jacobian [T, 3, 6, 39] (head and
 both feet; rows linear then angular, columns the root's linear and angular velocity then the 33 DoFs), mass_matrix [T, 39, 39] and
@@ -99,6 +103,9 @@ def run(args):
     if args.sensors_dir:
         cfg["sim"]["mi355"]["force_sensors"] = {"auto": True}
         os.makedirs(args.sensors_dir, exist_ok=True)
+    if args.scan_dir:
+        cfg["sim"]["mi355"]["height_scan"] = {"auto": True}
+        os.makedirs(args.scan_dir, exist_ok=True)
     if args.dynamics_dir:
         cfg["sim"]["mi355"]["jacobians"] = {"bodies": ["Head_Link", "L_Foot_Link", "R_Foot_Link"], "com_jacobian": True, "auto": True}
         if args.dynamics_forces:
@@ -125,6 +132,12 @@ def run(args):
         rec_sen = torch.zeros(args.max_steps, sensors_k, len(env.force_sensors.names), 6, device=dev)
         rec_cop = torch.zeros(args.max_steps, sensors_k, 2, 4, device=dev)
         rec_zmp = torch.zeros(args.max_steps, sensors_k, 4, device=dev)
+    scan_k = min(max(args.scan_envs, 1), args.num_envs) if args.scan_dir else 0
+    if scan_k:
+        hsc = env.height_scan
+        rec_hts = torch.zeros(args.max_steps, scan_k, hsc.heights.shape[1], device=dev)
+        rec_ppos = torch.zeros(args.max_steps, scan_k, len(hsc.names), 3, device=dev)
+        rec_clr = torch.zeros(args.max_steps, scan_k, len(hsc.names), device=dev)
     dynamics_k = min(max(args.dynamics_envs, 1), args.num_envs) if args.dynamics_dir else 0
     if dynamics_k:
         rec_jac = torch.zeros(args.max_steps, dynamics_k, 3, 6, 39, device=dev)
@@ -183,6 +196,10 @@ def run(args):
             rec_sen[_n].copy_(env.force_sensors.sensors[:sensors_k])
             rec_cop[_n].copy_(env.force_sensors.cop[:sensors_k])
             rec_zmp[_n].copy_(env.force_sensors.zmp[:sensors_k])
+        if scan_k:
+            rec_hts[_n].copy_(hsc.heights[:scan_k])
+            rec_ppos[_n].copy_(hsc.probe_pos[:scan_k])
+            rec_clr[_n].copy_(hsc.clearance[:scan_k])
         if dynamics_k:
             rec_jac[_n].copy_(env.jacobians.jacobian[:dynamics_k])
             rec_mm[_n].copy_(env.jacobians.mass_matrix[:dynamics_k])
@@ -258,6 +275,12 @@ def run(args):
             np.savez(os.path.join(args.bodies_dir, "bodies_env%d.npz" % e), names=np.asarray(bs.names), parents=np.asarray(bs.parents, np.int32),
                      dt=np.float64(bs.dt), states=rec_states[:played, e].cpu().numpy(), com=rec_com[:played, e].cpu().numpy())
         print("body states: %d steps of %d envs written to %s" % (played, bodies_k, args.bodies_dir), flush=True)
+    if scan_k:
+        import numpy as np
+        for e in range(scan_k):
+            np.savez(os.path.join(args.scan_dir, "scan_env%d.npz" % e), grid=hsc.grid, names=np.asarray(hsc.names), dt=np.float64(hsc.dt),
+                     heights=rec_hts[:played, e].cpu().numpy(), probe_pos=rec_ppos[:played, e].cpu().numpy(), clearance=rec_clr[:played, e].cpu().numpy())
+        print("height scan: %d steps of %d envs written to %s" % (played, scan_k, args.scan_dir), flush=True)
     if sensors_k:
         import numpy as np
         fs = env.force_sensors
@@ -319,6 +342,8 @@ def main():
     ap.add_argument("--gait-bins", type=int, default=72, choices=[12, 24, 36, 72, 144], help="phase bins of the gait profile")
     ap.add_argument("--bodies-dir", default=None, help="turn the rigid-body state tensor on and write bodies_env<id>.npz (every body's trajectory) here")
     ap.add_argument("--bodies-envs", type=int, default=1, help="record envs 0 .. K-1")
+    ap.add_argument("--scan-dir", default=None, help="turn the terrain height scan on and write scan_env<id>.npz (the heights around the base, the sole corners and their clearance) here")
+    ap.add_argument("--scan-envs", type=int, default=1, help="record envs 0 .. K-1")
     ap.add_argument("--sensors-dir", default=None, help="turn the foot force-torque sensors on and write sensors_env<id>.npz (wrenches, centres of pressure, ZMP) here")
     ap.add_argument("--sensors-envs", type=int, default=1, help="record envs 0 .. K-1")
     ap.add_argument("--dynamics-dir", default=None, help="turn the Jacobian and mass-matrix tensors on and write dynamics_env<id>.npz (head and foot Jacobians, M, COM Jacobian) here")

@@ -28,11 +28,11 @@ SOURCES = [("dw_hip.hip", []),
            ("dw_jacobian.hip", ["-ffp-contract=off"]), ("dw_dynamics.hip", ["-ffp-contract=off"]),
            ("dw_forward_dynamics.hip", ["-ffp-contract=off"]), ("dw_contact_dynamics.hip", ["-ffp-contract=off"]),
            ("dw_contact_inverse.hip", ["-ffp-contract=off"]),
-           ("dw_inverse_kinematics.hip", ["-ffp-contract=off"])]
+           ("dw_inverse_kinematics.hip", ["-ffp-contract=off"]), ("dw_height_scan.hip", ["-ffp-contract=off"])]
 HEADERS = ["dw_wave.h", "dw_devmodel.h", "dw_physics.h", "dw_task.h", "dw_params.h", "dw_quad_wave.h", "dw_quad_model.h",
            "dw_limb.h", "dw_bufg.h", "dw_oct.h", "dw_oct_kernels.h", "dw_oct_post.h", "dw_handle.h", "dw_amp.h", "dw_amp_step.h",
            "dw_amp_motion.h", "dw_stats.h", "dw_amp_stats.h", "dw_trace.h", "dw_meter.h", "dw_gait.h", "dw_bodies.h", "dw_sensors.h", "dw_jacobian.h", "dw_dynamics.h", "dw_factor.h", "dw_contact.h",
-           "dw_group.h", "dw_factor_wave.h", "dw_contact_inverse.h", "dw_stance_inverse.h", "dw_inverse_kinematics.h"]
+           "dw_group.h", "dw_factor_wave.h", "dw_contact_inverse.h", "dw_stance_inverse.h", "dw_inverse_kinematics.h", "dw_height_scan.h"]
 # -fno-slp-vectorize: the SLP vectoriser packs adjacent scalar f32 math into v_pk_*_f32 pairs: in the octet step kernel 1 920
 # packed instructions replace 4 079 scalar ones, but 775 v_mov are added to form the pairs and the two-waves-per-SIMD build (256
 # registers) goes from 0 to 612 B of scratch: 0.149 -> 0.199 ms (round 3), re-measured in round 4 with -slp-threshold 2..16 (DESIGN.md
@@ -53,7 +53,7 @@ def stale() -> bool:
         return True
     t = os.path.getmtime(LIB)
     deps = [os.path.join(CSRC, f) for f in [s for s, _ in SOURCES] + HEADERS] + [os.path.join(os.path.dirname(PKG), "include", h) for h in ("dyros_walk.h", "dyros_ppo.h", "dyros_amp_disc.h",
-                                                                                                                                  "dyros_amp_policy.h", "dyros_stats.h", "dyros_amp_stats.h", "dyros_trace.h", "dyros_meter.h", "dyros_gait.h", "dyros_bodies.h", "dyros_sensors.h", "dyros_jacobians.h", "dyros_dynamics.h", "dyros_forward_dynamics.h", "dyros_contact_dynamics.h", "dyros_contact_inverse_dynamics.h", "dyros_stance_inverse_dynamics.h", "dyros_inverse_kinematics.h")]
+                                                                                                                                  "dyros_amp_policy.h", "dyros_stats.h", "dyros_amp_stats.h", "dyros_trace.h", "dyros_meter.h", "dyros_gait.h", "dyros_bodies.h", "dyros_sensors.h", "dyros_jacobians.h", "dyros_dynamics.h", "dyros_forward_dynamics.h", "dyros_contact_dynamics.h", "dyros_contact_inverse_dynamics.h", "dyros_stance_inverse_dynamics.h", "dyros_inverse_kinematics.h", "dyros_height_scan.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -118,8 +118,8 @@ class DyrosDynamicWalk(VecTask):
         if spec is not None and spec is not False:
             from .gait_profile import GaitProfile
             self.gait_profile = GaitProfile(self, spec)
-        # cfg sim.mi355.body_states, force_sensors, jacobians, dynamics, forward_dynamics, contact_dynamics, contact_inverse_dynamics, stance_inverse_dynamics, inverse_kinematics: the model tensors, one launch per
-        # refresh or call (isaacgymdyros_amd/model_tensors.py's tables, DESIGN.md sections 21-29); off: None, no buffer, and step() makes no
+        # cfg sim.mi355.body_states, force_sensors, jacobians, dynamics, forward_dynamics, contact_dynamics, contact_inverse_dynamics, stance_inverse_dynamics, inverse_kinematics, height_scan: the model tensors, one launch per
+        # refresh or call (isaacgymdyros_amd/model_tensors.py's tables, DESIGN.md sections 21-30); off: None, no buffer, and step() makes no
         # extra launch
         model_tensors.attach(self, self, self.cfg["sim"].get("mi355", {}))
 
@@ -420,6 +420,13 @@ class DyrosDynamicWalk(VecTask):
         d = super().reset()
         model_tensors.refresh_auto(self)
         return d
+
+    def get_heights(self):
+        """The reference's get_heights (tasks/anymal_terrain.py:513): one launch; the ground's heights [N, P] at the scan's grid around every
+        base, from the bound height_samples (zeros on the plane)."""
+        if self.height_scan is None:
+            raise RuntimeError("get_heights: set cfg sim.mi355.height_scan to use the terrain height scan")
+        return self.height_scan.refresh()
 
     def refresh_rigid_body_state_tensor(self):
         """Isaac Gym's call: one launch that brings env.body_states.states (and .com) up to date with root_states and dof_state."""

@@ -1,4 +1,4 @@
-"""What the model-tensor features share on the host (DESIGN.md sections 21-29): the tables of the features, FEATURES and SOLVERS, by which the env classes
+"""What the model-tensor features share on the host (DESIGN.md sections 21-30): the tables of the features, FEATURES, SOLVERS and SENSORS, by which the env classes
 and config.validate_cfg validate, attach and refresh them; the common front of their resolve(); and ModelTensor, the base of their classes.
 
 A feature is a module of this package with K, EXPORTS, DEFAULTS, declare, resolve and validate, and a class over one env object's bound
@@ -30,6 +30,16 @@ SOLVERS = (
 )
 
 
+# SENSORS holds what looks at the world around the robot rather than at the robot, walked last
+SENSORS = (
+    ("height_scan", "HeightScan", ("terrain",)),           # the ground's heights at a yaw-aligned grid around the base [N, P], the soles' clearance [N, B]
+)
+
+
+def _all():
+    return FEATURES + SOLVERS + SENSORS
+
+
 def _module(name):
     return importlib.import_module("." + name, __package__)
 
@@ -37,14 +47,14 @@ def _module(name):
 def validate_all(cfg: dict, prefix: str = "") -> None:
     """Every feature's validate() of cfg sim.mi355.<prefix><name>: ValueError before anything is loaded or allocated."""
     mi = cfg["sim"].get("mi355", {})
-    for name, _, extra in FEATURES + SOLVERS:
+    for name, _, extra in _all():
         if mi.get(prefix + name) is not None:
             _module(name).validate(mi[prefix + name], *(cfg.get(k) for k in extra))
 
 
 def attach(env, host, mi355: dict, prefix: str = "") -> None:
     """env.<name> of every feature: its object over host's bound buffers where mi355[<prefix><name>] switches it on, None otherwise."""
-    for name, cls, _ in FEATURES + SOLVERS:
+    for name, cls, _ in _all():
         spec = mi355.get(prefix + name)
         on = spec is not None and spec is not False          # (as validate reads it: {} is the default spec)
         f = getattr(_module(name), cls)(host, spec) if on else None
@@ -55,7 +65,7 @@ def attach(env, host, mi355: dict, prefix: str = "") -> None:
 
 def refresh_auto(env) -> None:
     """refresh() of every attached feature with "auto": True, in cfg order (after step(), reset_idx() and reset())."""
-    for name, _, _ in FEATURES + SOLVERS:
+    for name, _, _ in _all():
         f = getattr(env, name)
         if f is not None and f.auto:
             f.refresh()

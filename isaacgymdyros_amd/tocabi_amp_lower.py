@@ -175,7 +175,7 @@ class TocabiAMPLower(VecTask):
         self._amp_stats_on = cfg["sim"].get("mi355", {}).get("amp_episode_stats", False)
         if not isinstance(self._amp_stats_on, bool):
             raise ValueError("sim.mi355.amp_episode_stats must be True or False")
-        # cfg sim.mi355.amp_body_states, amp_force_sensors, amp_jacobians, amp_dynamics, amp_forward_dynamics, amp_contact_dynamics, amp_contact_inverse_dynamics, amp_stance_inverse_dynamics, amp_inverse_kinematics: the model
+        # cfg sim.mi355.amp_body_states, amp_force_sensors, amp_jacobians, amp_dynamics, amp_forward_dynamics, amp_contact_dynamics, amp_contact_inverse_dynamics, amp_stance_inverse_dynamics, amp_inverse_kinematics, amp_height_scan: the model
         # tensors over the physics host's bound buffers (isaacgymdyros_amd/model_tensors.py's tables, DESIGN.md sections 21-29); off: None.
         # This class' own keys for the same reason: the plain ones would reach the physics host
         model_tensors.validate_all(cfg, "amp_")
@@ -190,7 +190,7 @@ class TocabiAMPLower(VecTask):
         # (physx.num_position_iterations + num_velocity_iterations = the contact solver's iteration count, as the task yaml gives them:
         #  4 + 0 for this task, cfg/task/TocabiAMPLower.yaml)
         # (this class' own keys stay here, spelled out: tests/test_forward_dynamics.py and tests/test_contact_dynamics.py read them in this text)
-        pc["sim"]["mi355"].update({k: v for k, v in cfg["sim"].get("mi355", {}).items() if k not in ("amp_episode_stats", "amp_body_states", "amp_force_sensors", "amp_jacobians", "amp_dynamics", "amp_forward_dynamics", "amp_contact_dynamics", "amp_contact_inverse_dynamics", "amp_stance_inverse_dynamics", "amp_inverse_kinematics")})
+        pc["sim"]["mi355"].update({k: v for k, v in cfg["sim"].get("mi355", {}).items() if k not in ("amp_episode_stats", "amp_body_states", "amp_force_sensors", "amp_jacobians", "amp_dynamics", "amp_forward_dynamics", "amp_contact_dynamics", "amp_contact_inverse_dynamics", "amp_stance_inverse_dynamics", "amp_inverse_kinematics", "amp_height_scan")})
         pc["env"]["perturbation"] = False
         # spawn height: the reference's 0.89 (:394) puts the soles 2.2 cm INTO the plane in the initial pose; PhysX resolves that
         # positionally, this simulator's contact model through a velocity bias (erp), which launches the robot at 2 m/s.  Default
@@ -971,6 +971,13 @@ class TocabiAMPLower(VecTask):
         if self.force_sensors is None:
             raise RuntimeError("refresh_force_sensor_tensor: set cfg sim.mi355.amp_force_sensors to use the foot force-torque sensors")
         return self.force_sensors.refresh()
+
+    def get_heights(self):
+        """The reference's get_heights: one launch; the ground's heights [N, P] at the scan's grid around every base (this task runs on the
+        plane: zeros)."""
+        if self.height_scan is None:
+            raise RuntimeError("get_heights: set cfg sim.mi355.amp_height_scan to use the terrain height scan")
+        return self.height_scan.refresh()
 
     def refresh_rigid_body_state_tensor(self):
         """Isaac Gym's call: one launch that brings amp.body_states.states (and .com) up to date with the physics' buffers."""
