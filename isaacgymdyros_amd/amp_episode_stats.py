@@ -17,9 +17,9 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, cbind
-from .cbind import check as _check
+from . import cbind
 from .ppo_update import _req
+from .recorders import EpisodeWindow, Window, div
 from .tocabi_amp_lower import REWARD_NAMES
 
 K = cbind.constants("dyros_amp_stats.h", "dwe_")
@@ -40,54 +40,36 @@ def mask_name(m: int) -> str:
 
 def fold(out, max_episode_length: float, body_names, command_x) -> dict:
     """The summary dict from dwe_summarize's [DWE_SUM_WORDS] doubles (a sequence of Python floats)."""
-    k = K
-    ct = lambda i: int(out[i])                                   # noqa: E731
-    ac = lambda i: float(out[k["DWE_SUM_AC"] + i])               # noqa: E731
-    div = lambda a, b: a / b if b else float("nan")              # noqa: E731
-    eps, samples = ct(k["DWE_CT_EPISODES"]), ct(k["DWE_CT_SAMPLES"])
-    masks = {m: ct(k["DWE_CT_MASK"] + m) for m in range(k["DWE_MASKS"])}
-    causes = {n: sum(v for m, v in masks.items() if m & b) for n, b in CAUSE_BITS.items()}
-    bodies = {body_names[g]: ct(k["DWE_CT_BODY"] + g) for g in range(len(body_names))}
+    w = Window(out, K, "DWE_")
+    ct, ac = w.ct, w.ac
+    masks = {m: ct("MASK", m) for m in range(K["DWE_MASKS"])}
+    s = w.head({n: sum(v for m, v in masks.items() if m & b) for n, b in CAUSE_BITS.items()}, body_names, max_episode_length)
+    samples = ct("SAMPLES")
     lo, hi = float(command_x[0]), float(command_x[1])
-    nb = k["DWE_CMD_BINS"]
+    nb = K["DWE_CMD_BINS"]
     bins = []
     for b in range(nb):
-        steps = ac(k["DWE_AC_VCNT"] + b)
+        steps = ac("VCNT", b)
         bins.append(dict(lo=lo + (hi - lo) * b / nb, hi=lo + (hi - lo) * (b + 1) / nb, steps=int(round(steps)),
-                         x_vel_error=div(ac(k["DWE_AC_VERR"] + b), steps)))
-    return dict(
-        records=ct(k["DWE_CT_RECORDS"]), episodes=eps, discarded=ct(k["DWE_CT_DISCARDED"]), unreset_steps=ct(k["DWE_CT_UNRESET"]),
-        nonfinite_steps=ct(k["DWE_CT_NONFINITE"]), sampled_steps=samples,
-        causes=causes, cause_fractions={n: div(v, eps) for n, v in causes.items()},
+                         x_vel_error=div(ac("VERR", b), steps)))
+    s.update(
+        discarded=ct("DISCARDED"), unreset_steps=ct("UNRESET"), nonfinite_steps=ct("NONFINITE"), sampled_steps=samples,
         cause_masks={mask_name(m): v for m, v in masks.items() if v},
-        contact_bodies={n: v for n, v in bodies.items() if v},
-        mean_length=div(ct(k["DWE_CT_LEN_SUM"]), eps), max_length=ct(k["DWE_CT_LEN_MAX"]),
-        length_hist=[ct(k["DWE_CT_LEN_HIST"] + i) for i in range(k["DWE_LEN_BINS"])],
-        length_edges=[max_episode_length * i / k["DWE_LEN_BINS"] for i in range(k["DWE_LEN_BINS"] + 1)],
-        mean_return=div(ac(k["DWE_AC_RET"]), eps),
-        reward_terms={n: div(ac(k["DWE_AC_REW"] + i), samples) for i, n in enumerate(REWARD_NAMES)},
+        reward_terms={n: div(ac("REW", i), samples) for i, n in enumerate(REWARD_NAMES)},
         command_bins=bins,
-        yaw_vel_error=div(ac(k["DWE_AC_YAW"]), samples),
-        sole_peak_mean=[div(ac(k["DWE_AC_PK"] + f), eps) for f in range(2)],
-        sole_over_threshold=[div(ct(k["DWE_CT_SOLE_OVER"] + f), samples) for f in range(2)],
-        record_calls=ct(k["DWE_CT_CALLS"]))
+        yaw_vel_error=div(ac("YAW"), samples),
+        sole_over_threshold=[div(ct("SOLE_OVER", f), samples) for f in range(2)])
+    return s
 
 
-class AmpEpisodeStats:
+class AmpEpisodeStats(EpisodeWindow):
     """The statistics of one TocabiAMPLower env (see the module docstring).  Buffers are allocated here, once."""
 
     CAUSE_BITS = CAUSE_BITS
 
     def __init__(self, env):
-        self.api = declare(_lib.load()[0])
-        self.env = env
-        N, dev = env.num_envs, env._tdev
-        self.num_envs = N
-        self.st = torch.zeros(K["DWE_ST_WORDS"], N, dtype=torch.int32, device=dev)
-        self.ac = torch.zeros(K["DWE_AC_WORDS"], N, dtype=torch.float32, device=dev)
-        self.ct = torch.zeros(K["DWE_CT_WORDS"], dtype=torch.int64, device=dev)          # (uint64 on the device side)
-        self.cause = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self.out = torch.zeros(K["DWE_SUM_WORDS"], dtype=torch.float64, device=dev)
+        super().__init__(env, declare, K, "DWE_")
+        N = self.num_envs
         self.body_names = list(env._phys.model.body_names)          # (Gym rows: 8 and 16 are L_Foot_Link / R_Foot_Link)
         assert len(self.body_names) == K["DWE_BODIES"]
         nb = env.num_bodies
@@ -106,12 +88,9 @@ class AmpEpisodeStats:
                       float(env.c_x[0]), float(env.c_x[1]))
         self.restart()
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.env._tdev).cuda_stream
-
     def record(self):
         """After a step, on the step's stream (the last call of TocabiAMPLower._step_body)."""
-        _check(self.api, self.api["record"](*self._args, self._stream()))
+        self._launch("record", self._args)
 
     def restart(self, env_ids: torch.Tensor = None):
         """Forgets the running episode of env_ids (None: every env): it is not counted, and the env's next record starts a new one."""
@@ -119,16 +98,6 @@ class AmpEpisodeStats:
             self.st[K["DWE_ST_N"]].fill_(-1)
         else:
             self.st[K["DWE_ST_N"]].index_fill_(0, env_ids.to(self.st.device).long(), -1)
-
-    def reset_totals(self):
-        """Starts a new window."""
-        self.ac.zero_()
-        self.ct[:K["DWE_CT_WINDOW"]].zero_()
-
-    def raw(self) -> list:
-        """dwe_summarize's doubles (one launch, one device-to-host copy)."""
-        _check(self.api, self.api["summarize"](self.num_envs, self.ac.data_ptr(), self.ct.data_ptr(), self.out.data_ptr(), self._stream()))
-        return self.out.cpu().tolist()
 
     def summary(self) -> dict:
         return fold(self.raw(), float(self.env.max_episode_length), self.body_names, self.env.c_x)

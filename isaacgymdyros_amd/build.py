@@ -32,7 +32,7 @@ SOURCES = [("dw_hip.hip", []),
 HEADERS = ["dw_wave.h", "dw_devmodel.h", "dw_physics.h", "dw_task.h", "dw_params.h", "dw_quad_wave.h", "dw_quad_model.h",
            "dw_limb.h", "dw_bufg.h", "dw_oct.h", "dw_oct_kernels.h", "dw_oct_post.h", "dw_handle.h", "dw_amp.h", "dw_amp_step.h",
            "dw_amp_motion.h", "dw_stats.h", "dw_amp_stats.h", "dw_trace.h", "dw_meter.h", "dw_gait.h", "dw_bodies.h", "dw_sensors.h", "dw_jacobian.h", "dw_dynamics.h", "dw_factor.h", "dw_contact.h",
-           "dw_group.h", "dw_factor_wave.h", "dw_contact_inverse.h", "dw_stance_inverse.h", "dw_inverse_kinematics.h", "dw_height_scan.h"]
+           "dw_group.h", "dw_episode.h", "dw_record_group.h", "dw_factor_wave.h", "dw_contact_inverse.h", "dw_stance_inverse.h", "dw_inverse_kinematics.h", "dw_height_scan.h"]
 # -fno-slp-vectorize: the SLP vectoriser packs adjacent scalar f32 math into v_pk_*_f32 pairs: in the octet step kernel 1 920
 # packed instructions replace 4 079 scalar ones, but 775 v_mov are added to form the pairs and the two-waves-per-SIMD build (256
 # registers) goes from 0 to 612 B of scratch: 0.149 -> 0.199 ms (round 3), re-measured in round 4 with -slp-threshold 2..16 (DESIGN.md

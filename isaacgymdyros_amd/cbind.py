@@ -157,3 +157,16 @@ def check(api: dict, rc: int):
     """Every entry point returns 0 or an error code, with the message in its ABI's last_error()."""
     if rc != 0:
         raise DyrosWalkLibraryError("%s (code %d)" % (api["last_error"]().decode(), rc))
+
+
+class Launcher:
+    """The base of the classes that launch an ABI's entry points on torch's current stream (recorders.Recorder, model_tensors.ModelTensor):
+    self.api is the declared ABI, self._tdev the torch device."""
+
+    def _stream(self) -> int:
+        import torch
+        return torch.cuda.current_stream(self._tdev).cuda_stream
+
+    def _launch(self, entry: str, args: tuple) -> None:
+        """One launch on torch's current stream."""
+        check(self.api, self.api[entry](*args, self._stream()))

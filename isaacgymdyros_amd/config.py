@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import copy
 
-from . import model_tensors
+from . import model_tensors, recorders
 
 
 def default_cfg(num_envs: int = 4096, sim_device: str = "cuda:0") -> dict:
@@ -104,14 +104,7 @@ def validate_cfg(cfg: dict) -> None:
         raise ValueError("sim.mi355.debug_wave_build must be 0 (by launch size), 1 / 2 (octet kernels: one / two waves per SIMD) or 3 (hex instantiation)")
     if sim.get("mi355", {}).get("pipeline", 0) not in (0, 3, "auto", "oct"):
         raise ValueError("sim.mi355.pipeline must be 0/'auto' or 3/'oct' (1/'fused', 2/'quad' and 4/'lane', the kernels of rounds 1, 2 and 4, are retired)")
-    if not isinstance(sim.get("mi355", {}).get("episode_stats", False), bool):
-        raise ValueError("sim.mi355.episode_stats must be True or False")
-    if sim.get("mi355", {}).get("run_trace") is not None:
-        from .run_trace import validate as validate_run_trace          # (env ids in range and distinct, depth, hold mode, ring size)
-        validate_run_trace(sim["mi355"]["run_trace"], n)
-    if sim.get("mi355", {}).get("gait_profile") is not None:
-        from .gait_profile import validate as validate_gait_profile          # (bins one of 12, 24, 36, 72, 144; the two filters)
-        validate_gait_profile(sim["mi355"]["gait_profile"])
+    recorders.validate_all(cfg, n)          # (episode_stats, run_trace, gait_profile: isaacgymdyros_amd/recorders.py's table)
     for prefix in ("", "amp_"):          # (the model tensors: isaacgymdyros_amd/model_tensors.py's table; amp_: TocabiAMPLower's keys)
         model_tensors.validate_all(cfg, prefix)
     iters = int(px.get("num_position_iterations", 4)) + int(px.get("num_velocity_iterations", 1))

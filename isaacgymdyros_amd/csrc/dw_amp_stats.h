@@ -6,20 +6,13 @@
 
 #include <math.h>
 #include <stdint.h>
-#include <string.h>
 
 #include "dw_amp.h"
 #include "../../include/dyros_amp_stats.h"
+#include "dw_episode.h"
 
 #if defined(__clang__)
 #pragma clang fp contract(off)
-#endif
-
-// (member functions: DW_HD is `static inline` under a host compiler)
-#if defined(__HIPCC__)
-#define DWE_M __device__ __forceinline__
-#else
-#define DWE_M inline
 #endif
 
 namespace dwe {
@@ -27,21 +20,19 @@ namespace dwe {
 constexpr int NB = DWE_BODIES;
 static_assert(NB == DW_NUM_BODIES, "contact_forces / rigid_body_pos rows");
 
-DW_HD float u2f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-DW_HD uint32_t f2u(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+using epi::f2u;
+using epi::partial;
+using epi::Rows;
+using epi::RT;
+using epi::u2f;
 
 // a component over 1 (the step tests components, not the norm)
-DW_HD bool over_1(float x, float y, float z) { return x > 1.0f || y > 1.0f || z > 1.0f; }
+struct Over1 {
+    EPI_HD bool operator()(float x, float y, float z) const { return x > 1.0f || y > 1.0f || z > 1.0f; }
+};
 
 // bit g of (lo | hi << 32): Gym body g (not a sole) has a component over 1
-DW_HD void contact_mask(const float *cf, uint32_t &lo, uint32_t &hi) {
-    lo = hi = 0u;
-    for (int g = 0; g < NB; ++g)
-        if (g != DWE_LFOOT && g != DWE_RFOOT && over_1(cf[3 * g], cf[3 * g + 1], cf[3 * g + 2])) {
-            if (g < 32) lo |= 1u << g;
-            else hi |= 1u << (g - 32);
-        }
-}
+DW_HD void contact_mask(const float *cf, uint32_t &lo, uint32_t &hi) { epi::contact_mask<NB, DWE_LFOOT, DWE_RFOOT>(cf, lo, hi, Over1{}); }
 
 struct Cfg {
     float max_len, term_h, cmd_lo, cmd_hi;
@@ -57,15 +48,6 @@ struct EnvIn {
     float zl, zr;             // rigid_body_pos[8 / 16][2]
     float rew, total_mass;
     int p, reset;
-};
-
-// SoA view of st / ac: word k of env e at k * n + e
-struct Rows {
-    uint32_t *st;
-    float *ac;
-    int n, e;
-    DWE_M uint32_t &w(int k) const { return st[(size_t)k * n + e]; }
-    DWE_M float &a(int k) const { return ac[(size_t)k * n + e]; }
 };
 
 // the running episode of one env (the DWE_ST_* words) and the window sums every record adds to, held in registers between one load and one
@@ -192,15 +174,6 @@ DW_HD int update(const EnvIn &in, uint32_t mlo, uint32_t mhi, St &s, AcHot &h, c
 DW_HD void count_call(uint64_t *ct) {
     ct[DWE_CT_CALLS] += 1;
     ct[DWE_CT_RECORDS] += 1;
-}
-
-// the fixed order of every float sum of dwe_summarize: RT partial sums in double over e = t, t + RT, ..., then a halving tree
-constexpr int RT = 256;
-
-DW_HD double partial(const float *row, int n, int t) {
-    double s = 0.0;
-    for (int e = t; e < n; e += RT) s += (double)row[e];
-    return s;
 }
 
 }  // namespace dwe

@@ -16,7 +16,7 @@
 
 namespace {
 
-dwg::Err s_err;
+grp::Err s_err;
 
 constexpr int G = DWB_GROUP, TPB = DWB_GROUP * DWB_LANES;
 static_assert(TPB % 64 == 0 && DWB_LANES == 16 && DWB_MAX_LEAVES <= DWB_LANES, "whole waves, sixteen lanes per env, room for a lane per path");
@@ -40,10 +40,10 @@ __global__ __launch_bounds__(TPB) void dwb_k_refresh(int n, const uint4 *__restr
     const int t = threadIdx.x, e0 = blockIdx.x * G;
     const int ne = n - e0 < G ? n - e0 : G;          // envs of this workgroup (the last one may hold fewer)
     // ---- loads: consecutive lanes, consecutive words ----
-    dwg::load_table<TPB, DWB_TABLE_WORDS>(table, t, s_tab4);
-    dwg::load_rows<TPB>(root_states, e0, ne, dwb::IN_ROOT, t, s_root);
-    dwg::load_rows<TPB>(dof_state, e0, ne, dwb::IN_DOF, t, s_dof);
-    if (mass_scale != nullptr && com != nullptr) dwg::load_rows<TPB>(mass_scale, e0, ne, dwb::NB, t, s_ms);
+    grp::load_table<TPB, DWB_TABLE_WORDS>(table, t, s_tab4);
+    grp::load_rows<TPB>(root_states, e0, ne, dwb::IN_ROOT, t, s_root);
+    grp::load_rows<TPB>(dof_state, e0, ne, dwb::IN_DOF, t, s_dof);
+    if (mass_scale != nullptr && com != nullptr) grp::load_rows<TPB>(mass_scale, e0, ne, dwb::NB, t, s_ms);
     __syncthreads();
     const dwb::Tab T{reinterpret_cast<const uint32_t *>(s_tab4)};
     if (t < nb) s_ids[t] = dwb::row_of(T, ids.b[t] < dwb::NB ? ids.b[t] : dwb::NB - 1);          // (read after the barrier below)
@@ -137,8 +137,7 @@ int dwb_refresh(int32_t num_envs, const uint32_t *table, const float *root_state
     }
     hipLaunchKernelGGL(dwb_k_refresh, dim3(dwb::groups(num_envs)), dim3(TPB), 0, (hipStream_t)stream, (int)num_envs,
                        reinterpret_cast<const uint4 *>(table), root_states, dof_state, mass_scale, ids, (int)nb, (int)(vel_at_com != 0), states, com);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : s_err.fail_hip("dwb_refresh: launch", e);
+    return s_err.launched("dwb_refresh");
 }
 
 }  // extern "C"

@@ -22,7 +22,7 @@
 
 namespace {
 
-dwg::Err s_err_i, s_err_k;          // (the error is per ABI)
+grp::Err s_err_i, s_err_k;          // (the error is per ABI)
 
 constexpr int G = DWI_GROUP, L = DWI_LANES, TPB = DWI_GROUP * DWI_LANES;
 constexpr int IN_ROOT = dwb::IN_ROOT, IN_DOF = dwb::IN_DOF, NV = dwi::NV, NB = dwi::NB, ND = dwi::ND, GN = dwi::GN, MAXM = dwi::MAXM, MW = dwk::MW;
@@ -55,12 +55,12 @@ __device__ __forceinline__ void solve(int n, const uint4 *__restrict__ table, co
     const bool need_r = need_f || tau_full != nullptr;
     const int what = need_r ? dwn::W_TAU : 0;
     const bool has_acc = accel != nullptr, has_ms = mass_scale != nullptr, has_arm = has_acc && dof_armature != nullptr;
-    dwg::load_table<TPB, TABLE_WORDS>(table, t, s_tab4);
-    dwg::load_rows<TPB>(root_states, e0, ne, IN_ROOT, t, s_root);
-    dwg::load_rows<TPB>(dof_state, e0, ne, IN_DOF, t, s_dof);
-    if (has_ms && need_r) dwg::load_rows<TPB>(mass_scale, e0, ne, NB, t, s_ms);
-    if (has_arm && need_r) dwg::load_rows<TPB>(dof_armature, e0, ne, ND, t, s_arm);
-    if (has_acc) dwg::load_rows<TPB>(accel, e0, ne, NV, t, s_acc);
+    grp::load_table<TPB, TABLE_WORDS>(table, t, s_tab4);
+    grp::load_rows<TPB>(root_states, e0, ne, IN_ROOT, t, s_root);
+    grp::load_rows<TPB>(dof_state, e0, ne, IN_DOF, t, s_dof);
+    if (has_ms && need_r) grp::load_rows<TPB>(mass_scale, e0, ne, NB, t, s_ms);
+    if (has_arm && need_r) grp::load_rows<TPB>(dof_armature, e0, ne, ND, t, s_arm);
+    if (has_acc) grp::load_rows<TPB>(accel, e0, ne, NV, t, s_acc);
     __syncthreads();
     const dwb::Tab T{reinterpret_cast<const uint32_t *>(s_tab4)};
     const float g[3] = {gx, gy, gz};
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(TPB) void dwk_k_solve(int n, const uint4 *__restric
 
 // the refusals both entry points share, under the caller's name `who`, then the launch: the kernel's arguments after gz are `rest`
 template <class Kernel, class... Rest>
-int launch(dwg::Err &err, const char *who, Kernel kernel, bool any_output, void *stream, int32_t num_envs, const uint32_t *table, const float *root_states,
+int launch(grp::Err &err, const char *who, Kernel kernel, bool any_output, void *stream, int32_t num_envs, const uint32_t *table, const float *root_states,
            const float *dof_state, const float *mass_scale, const float *dof_armature, float gx, float gy, float gz, Rest... rest) {
     if (num_envs < 1 || num_envs > 0x7fffffff / (IN_DOF + NV) - G) return err.fail(who, "num_envs must be in [1, 2^31 / 105 - 4)");
     if (!table || !root_states || !dof_state) return err.fail(who, "a buffer is missing");

@@ -18,7 +18,7 @@
 
 namespace {
 
-dwg::Err s_err;
+grp::Err s_err;
 
 constexpr int G = DWN_GROUP, TPB = DWN_GROUP * DWN_LANES;
 constexpr int IN_ROOT = dwb::IN_ROOT, IN_DOF = dwb::IN_DOF, NV = dwn::NV, NB = dwn::NB, ND = DWN_NUM_DOF;
@@ -29,7 +29,7 @@ static_assert((DWN_TABLE_WORDS + G * (IN_ROOT + IN_DOF + NB + ND + NV + dwn::ENV
 
 // the group's contiguous block of an output, rows of `row` words at word `at` of each env's OUT: 16 bytes per lane where dst is aligned
 __device__ __forceinline__ void store_rows(float *__restrict__ dst, int e0, int ne, int row, int at, int t, const float *s_env) {
-    dwg::store_block<TPB>(dst + (size_t)e0 * row, ne * row, (reinterpret_cast<uintptr_t>(dst) & 15u) == 0u, t, [&](int idx) {
+    grp::store_block<TPB>(dst + (size_t)e0 * row, ne * row, (reinterpret_cast<uintptr_t>(dst) & 15u) == 0u, t, [&](int idx) {
         const int e = idx / row;
         return s_env[e * dwn::ENV + dwn::E_OUT + at + (idx - row * e)];
     });
@@ -52,12 +52,12 @@ __global__ __launch_bounds__(TPB) void dwn_k_inverse_dynamics(int n, const uint4
     const int what = (bias != nullptr ? dwn::W_BIAS : 0) | (gravity != nullptr ? dwn::W_GRAV : 0) | (tau != nullptr && accel != nullptr ? dwn::W_TAU : 0) |
                      (momentum != nullptr ? dwn::W_MOM : 0);
     const bool has_acc = (what & dwn::W_TAU) != 0, has_ms = mass_scale != nullptr, has_arm = has_acc && dof_armature != nullptr;
-    dwg::load_table<TPB, DWN_TABLE_WORDS>(table, t, s_tab4);
-    dwg::load_rows<TPB>(root_states, e0, ne, IN_ROOT, t, s_root);
-    dwg::load_rows<TPB>(dof_state, e0, ne, IN_DOF, t, s_dof);
-    if (has_ms) dwg::load_rows<TPB>(mass_scale, e0, ne, NB, t, s_ms);
-    if (has_arm) dwg::load_rows<TPB>(dof_armature, e0, ne, ND, t, s_arm);
-    if (has_acc) dwg::load_rows<TPB>(accel, e0, ne, NV, t, s_acc);
+    grp::load_table<TPB, DWN_TABLE_WORDS>(table, t, s_tab4);
+    grp::load_rows<TPB>(root_states, e0, ne, IN_ROOT, t, s_root);
+    grp::load_rows<TPB>(dof_state, e0, ne, IN_DOF, t, s_dof);
+    if (has_ms) grp::load_rows<TPB>(mass_scale, e0, ne, NB, t, s_ms);
+    if (has_arm) grp::load_rows<TPB>(dof_armature, e0, ne, ND, t, s_arm);
+    if (has_acc) grp::load_rows<TPB>(accel, e0, ne, NV, t, s_acc);
     __syncthreads();
     const dwb::Tab T{reinterpret_cast<const uint32_t *>(s_tab4)};
     const float g[3] = {gx, gy, gz};
@@ -106,8 +106,7 @@ int dwn_inverse_dynamics(int32_t num_envs, const uint32_t *table, const float *r
     hipLaunchKernelGGL(dwn_k_inverse_dynamics, dim3(dwn::groups(num_envs)), dim3(TPB), 0, (hipStream_t)stream, (int)num_envs,
                        reinterpret_cast<const uint4 *>(table), root_states, dof_state, mass_scale, dof_armature, gx, gy, gz, accel,
                        (int)(vel_at_com != 0), bias, gravity, tau, momentum);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : s_err.fail_hip("dwn_inverse_dynamics: launch", e);
+    return s_err.launched("dwn_inverse_dynamics");
 }
 
 }  // extern "C"

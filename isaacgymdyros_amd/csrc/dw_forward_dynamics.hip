@@ -20,7 +20,7 @@
 
 namespace {
 
-dwg::Err s_err;
+grp::Err s_err;
 
 constexpr int G = DWL_GROUP, L = DWL_LANES, TPB = DWL_GROUP * DWL_LANES;
 constexpr int IN_ROOT = dwb::IN_ROOT, IN_DOF = dwb::IN_DOF, NV = dwl::NV, NB = dwl::NB, ND = DWL_NUM_DOF, MMW = dwl::MMW;
@@ -43,11 +43,11 @@ __global__ __launch_bounds__(TPB) void dwl_k_solve(int n, const uint4 *__restric
     const int t = threadIdx.x, e0 = blockIdx.x * G;
     const int ne = n - e0 < G ? n - e0 : G;          // envs of this workgroup (the last one may hold fewer)
     const bool has_ms = mass_scale != nullptr, has_arm = dof_armature != nullptr;
-    dwg::load_table<TPB, DWL_TABLE_WORDS>(table, t, s_tab4);
-    dwg::load_rows<TPB>(root_states, e0, ne, IN_ROOT, t, s_root);
-    dwg::load_rows<TPB>(dof_state, e0, ne, IN_DOF, t, s_dof);
-    if (has_ms) dwg::load_rows<TPB>(mass_scale, e0, ne, NB, t, s_ms);
-    if (has_arm) dwg::load_rows<TPB>(dof_armature, e0, ne, ND, t, s_arm);
+    grp::load_table<TPB, DWL_TABLE_WORDS>(table, t, s_tab4);
+    grp::load_rows<TPB>(root_states, e0, ne, IN_ROOT, t, s_root);
+    grp::load_rows<TPB>(dof_state, e0, ne, IN_DOF, t, s_dof);
+    if (has_ms) grp::load_rows<TPB>(mass_scale, e0, ne, NB, t, s_ms);
+    if (has_arm) grp::load_rows<TPB>(dof_armature, e0, ne, ND, t, s_arm);
     __syncthreads();
     const dwb::Tab T{reinterpret_cast<const uint32_t *>(s_tab4)};
     const int nleaf = T.nleaf();
@@ -134,8 +134,7 @@ int dwl_solve(int32_t num_envs, const uint32_t *table, const float *root_states,
     hipLaunchKernelGGL(dwl_k_solve, dim3(dwl::groups(num_envs)), dim3(TPB), 0, (hipStream_t)stream, (int)num_envs,
                        reinterpret_cast<const uint4 *>(table), root_states, dof_state, mass_scale, dof_armature, (int)(vel_at_com != 0), rhs,
                        (int)(rhs ? nrhs : 0), sub, x, factor, minv);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : s_err.fail_hip("dwl_solve: launch", e);
+    return s_err.launched("dwl_solve");
 }
 
 }  // extern "C"

@@ -8,16 +8,12 @@
 //                other workgroup touches it), and the four counters with one 64-bit atomic each.
 //   k_summarize  one lane per table word: the sum of the partial tables in workgroup order (any order gives the same integers).
 //   k_clear      zeroes the partial tables and the counters.
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-
+#include "dw_group.h"
 #include "dw_gait.h"
 
 namespace {
 
-char s_err[256] = "";
-int fail(const char *msg) { snprintf(s_err, sizeof(s_err), "%s", msg); return -1; }
-int fail_hip(const char *who, hipError_t e) { snprintf(s_err, sizeof(s_err), "%s: %s", who, hipGetErrorString(e)); return -1; }
+grp::Err s_err;
 
 constexpr int EPB = DWG_GROUP, TPB = 256;
 constexpr int JW = 3 * dwg::NJ;                       // staged words per env: dof_pos, target_qpos, action_torque
@@ -133,16 +129,8 @@ __global__ __launch_bounds__(256) void dwg_k_clear(size_t words, long long *part
 }
 
 int check_shape(const char *who, int32_t num_envs, int32_t bins) {
-    static char msg[128];
-    if (num_envs < 1 || num_envs > 0x7fffffff - EPB) {
-        snprintf(msg, sizeof(msg), "%s: num_envs must be in [1, 2^31 - %d)", who, EPB);
-        return fail(msg);
-    }
-    if (!dwg::bins_ok(bins)) {
-        snprintf(msg, sizeof(msg), "%s: bins must be one of 12, 24, 36, 72, 144", who);
-        return fail(msg);
-    }
-    return 0;
+    if (s_err.envs(who, num_envs, EPB) != 0) return -1;
+    return dwg::bins_ok(bins) ? 0 : s_err.fail(who, "bins must be one of 12, 24, 36, 72, 144");
 }
 
 }  // namespace
@@ -150,7 +138,7 @@ int check_shape(const char *who, int32_t num_envs, int32_t bins) {
 extern "C" {
 
 int dwg_abi_version(void) { return DWG_ABI_VERSION; }
-const char *dwg_last_error(void) { return s_err; }
+const char *dwg_last_error(void) { return s_err.s; }
 
 int64_t dwg_groups(int32_t num_envs) {
     if (num_envs < 1 || num_envs > 0x7fffffff - EPB) return -1;
@@ -161,37 +149,34 @@ int dwg_record(int32_t num_envs, int32_t bins, int32_t min_episode_step, int32_t
                const float *contact_forces, const float *env_state, const float *stacked_rewards, const int64_t *reset_buf,
                const int64_t *progress_buf, const float *total_mass, int64_t *part, int64_t *ct, void *stream) {
     if (check_shape("dwg_record", num_envs, bins) != 0) return -1;
-    if (min_episode_step < 0) return fail("dwg_record: min_episode_step must not be negative");
+    if (min_episode_step < 0) return s_err.fail("dwg_record: min_episode_step must not be negative");
     if (!root_states || !dof_state || !contact_forces || !env_state || !stacked_rewards || !reset_buf || !progress_buf || !total_mass || !part || !ct)
-        return fail("dwg_record: a buffer is missing");
+        return s_err.fail("dwg_record: a buffer is missing");
     if ((reinterpret_cast<uintptr_t>(part) & 7u) != 0u || (reinterpret_cast<uintptr_t>(ct) & 7u) != 0u)
-        return fail("dwg_record: part and ct must be 8-byte aligned");
+        return s_err.fail("dwg_record: part and ct must be 8-byte aligned");
     hipLaunchKernelGGL(dwg_k_record, dim3(dwg::groups(num_envs)), dim3(TPB), 0, (hipStream_t)stream, (int)num_envs, (int)bins, (int)min_episode_step,
                        (int)(skip_pushes != 0), root_states, dof_state, contact_forces, env_state, stacked_rewards, reset_buf, progress_buf, total_mass,
                        (long long *)part, (unsigned long long *)ct);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dwg_record: launch", e);
+    return s_err.launched("dwg_record");
 }
 
 int dwg_clear(int32_t num_envs, int32_t bins, int64_t *part, int64_t *ct, void *stream) {
     if (check_shape("dwg_clear", num_envs, bins) != 0) return -1;
-    if (!part || !ct) return fail("dwg_clear: a buffer is missing");
+    if (!part || !ct) return s_err.fail("dwg_clear: a buffer is missing");
     const size_t words = (size_t)dwg::groups(num_envs) * bins * dwg::W;
     const size_t blocks = (words + 255) / 256;
     hipLaunchKernelGGL(dwg_k_clear, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, (hipStream_t)stream, words, (long long *)part,
                        (long long *)ct);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dwg_clear: launch", e);
+    return s_err.launched("dwg_clear");
 }
 
 int dwg_summarize(int32_t num_envs, int32_t bins, const int64_t *part, const int64_t *ct, int64_t *out, void *stream) {
     if (check_shape("dwg_summarize", num_envs, bins) != 0) return -1;
-    if (!part || !ct || !out) return fail("dwg_summarize: a buffer is missing");
+    if (!part || !ct || !out) return s_err.fail("dwg_summarize: a buffer is missing");
     const int words = bins * dwg::W;
     hipLaunchKernelGGL(dwg_k_summarize, dim3((words + DWG_CT_WORDS + 255) / 256), dim3(256), 0, (hipStream_t)stream, dwg::groups(num_envs), words,
                        (const long long *)part, (const long long *)ct, (long long *)out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dwg_summarize: launch", e);
+    return s_err.launched("dwg_summarize");
 }
 
 }  // extern "C"

@@ -17,7 +17,7 @@
 
 namespace {
 
-dwg::Err s_err;
+grp::Err s_err;
 
 constexpr int G = DWH_GROUP, TPB = DWH_GROUP * DWH_LANES, NPR = DWH_MAX_PROBES;
 // the largest map side for which terrain_sample's upper clamp, (float)(rows - 1) - 1e-3f, still lies below the last sample line in float32
@@ -40,9 +40,9 @@ __global__ __launch_bounds__(TPB) void dwh_k_scan(int n, const uint4 *__restrict
     __shared__ int s_ok[G];
     const int t = threadIdx.x, e0 = blockIdx.x * G;
     const int ne = n - e0 < G ? n - e0 : G;          // envs of this workgroup (the last one may hold fewer)
-    dwg::load_table<TPB, DWH_TABLE_WORDS>(table, t, s_tab4);
-    dwg::load_rows<TPB>(root_states, e0, ne, dwh::IN_ROOT, t, s_root);
-    dwg::load_rows<TPB>(dof_state, e0, ne, dwh::IN_DOF, t, s_dof);
+    grp::load_table<TPB, DWH_TABLE_WORDS>(table, t, s_tab4);
+    grp::load_rows<TPB>(root_states, e0, ne, dwh::IN_ROOT, t, s_root);
+    grp::load_rows<TPB>(dof_state, e0, ne, dwh::IN_DOF, t, s_dof);
     __syncthreads();
     const dwh::Tab T{dwb::Tab{reinterpret_cast<const uint32_t *>(s_tab4)}};
     const int P = T.np(), B = T.nb(), NW = T.nw();
@@ -153,8 +153,7 @@ int dwh_scan(int32_t num_envs, const uint32_t *table, const float *root_states, 
     const Out out = {heights, points, obs, probe_pos, probe_height, clearance, probe_normal};
     hipLaunchKernelGGL(dwh_k_scan, dim3(dwh::groups(num_envs)), dim3(TPB), 0, (hipStream_t)stream, (int)num_envs,
                        reinterpret_cast<const uint4 *>(table), root_states, dof_state, M, (int)rule, out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : s_err.fail_hip("dwh_scan: launch", e);
+    return s_err.launched("dwh_scan");
 }
 
 }  // extern "C"

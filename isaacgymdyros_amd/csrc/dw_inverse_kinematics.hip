@@ -19,7 +19,7 @@
 
 namespace {
 
-dwg::Err s_err;
+grp::Err s_err;
 
 constexpr int G = DWQ_GROUP, L = DWQ_LANES, TPB = DWQ_GROUP * DWQ_LANES;
 constexpr int IN_ROOT = dwb::IN_ROOT, IN_DOF = dwb::IN_DOF, NV = dwq::NV, ND = dwq::ND, MAXM = dwq::MAXM, MAXK = dwq::MAXK, TW = dwq::TW, ENV = dwq::ENV;
@@ -39,9 +39,9 @@ __global__ __launch_bounds__(TPB) void dwq_k_solve(int n, const uint4 *__restric
     __shared__ float s_env[G * ENV];
     const int t = threadIdx.x, e0 = blockIdx.x * G;
     const int ne = n - e0 < G ? n - e0 : G;          // envs of this workgroup (the last one may hold fewer)
-    dwg::load_table<TPB, DWQ_TABLE_WORDS>(table, t, s_tab4);
-    dwg::load_rows<TPB>(root_states, e0, ne, IN_ROOT, t, s_root);
-    dwg::load_rows<TPB>(dof_state, e0, ne, IN_DOF, t, s_dof);
+    grp::load_table<TPB, DWQ_TABLE_WORDS>(table, t, s_tab4);
+    grp::load_rows<TPB>(root_states, e0, ne, IN_ROOT, t, s_root);
+    grp::load_rows<TPB>(dof_state, e0, ne, IN_DOF, t, s_dof);
     __syncthreads();
     const dwb::Tab T{reinterpret_cast<const uint32_t *>(s_tab4)};
     const int nleaf = T.nleaf(), K = dwq::count(T), m = 6 * K, I = dwq::iterations(T);
@@ -168,8 +168,7 @@ int dwq_solve(int32_t num_envs, const uint32_t *table, const float *root_states,
     if (!q && !root_out && !residual && !err && !iters && !converged) return s_err.fail(who, "no output: nothing to compute");
     hipLaunchKernelGGL(dwq_k_solve, dim3(dwq::groups(num_envs)), dim3(TPB), 0, (hipStream_t)stream, (int)num_envs, reinterpret_cast<const uint4 *>(table),
                        root_states, dof_state, q0, targets, q, root_out, residual, err, iters, converged);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : s_err.fail_hip("dwq_solve: launch", e);
+    return s_err.launched("dwq_solve");
 }
 
 }  // extern "C"

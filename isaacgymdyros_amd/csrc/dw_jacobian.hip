@@ -19,7 +19,7 @@
 
 namespace {
 
-dwg::Err s_err;
+grp::Err s_err;
 
 constexpr int G = DWJ_GROUP, TPB = DWJ_GROUP * DWJ_LANES;
 constexpr int IN_ROOT = dwb::IN_ROOT, IN_DOF = dwb::IN_DOF;
@@ -41,9 +41,9 @@ __global__ __launch_bounds__(TPB) void dwj_k_jacobian(int n, const uint4 *__rest
     __shared__ int s_rows[G * dwj::NB];          // the group's output rows resolved once: env << 25 | jac_row_of
     const int t = threadIdx.x, e0 = blockIdx.x * G;
     const int ne = n - e0 < G ? n - e0 : G;          // envs of this workgroup (the last one may hold fewer)
-    dwg::load_table<TPB, DWJ_TABLE_WORDS>(table, t, s_tab4);
-    dwg::load_rows<TPB>(root_states, e0, ne, IN_ROOT, t, s_root);
-    dwg::load_rows<TPB>(dof_state, e0, ne, IN_DOF, t, s_dof);
+    grp::load_table<TPB, DWJ_TABLE_WORDS>(table, t, s_tab4);
+    grp::load_rows<TPB>(root_states, e0, ne, IN_ROOT, t, s_root);
+    grp::load_rows<TPB>(dof_state, e0, ne, IN_DOF, t, s_dof);
     __syncthreads();
     const dwb::Tab T{reinterpret_cast<const uint32_t *>(s_tab4)};
     for (int i = t; i < ne * nb; i += TPB) {
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(TPB) void dwj_k_jacobian(int n, const uint4 *__rest
         __syncthreads();
     }
     const int rw = nb * dwj::JROW;
-    dwg::store_block<TPB>(jac + (size_t)e0 * rw, ne * rw, (reinterpret_cast<uintptr_t>(jac) & 15u) == 0u, t, [&](int idx) {
+    grp::store_block<TPB>(jac + (size_t)e0 * rw, ne * rw, (reinterpret_cast<uintptr_t>(jac) & 15u) == 0u, t, [&](int idx) {
         const int q = idx / dwj::NV, c = idx - dwj::NV * q, er = q / dwj::JR, i = q - dwj::JR * er;
         const int row = s_rows[er];
         return dwj::jac_word(T, s_env + (row >> 25) * dwj::JAC_ENV, row & 0x1ffffff, i, c);
@@ -85,11 +85,11 @@ __global__ __launch_bounds__(TPB) void dwj_k_mass_matrix(int n, const uint4 *__r
     __shared__ float s_env[G * dwj::MM_ENV];
     const int t = threadIdx.x, e0 = blockIdx.x * G;
     const int ne = n - e0 < G ? n - e0 : G;
-    dwg::load_table<TPB, DWJ_TABLE_WORDS>(table, t, s_tab4);
-    dwg::load_rows<TPB>(root_states, e0, ne, IN_ROOT, t, s_root);
-    dwg::load_rows<TPB>(dof_state, e0, ne, IN_DOF, t, s_dof);
-    if (mass_scale != nullptr) dwg::load_rows<TPB>(mass_scale, e0, ne, dwj::NB, t, s_ms);
-    if (dof_armature != nullptr) dwg::load_rows<TPB>(dof_armature, e0, ne, DWJ_NUM_DOF, t, s_arm);
+    grp::load_table<TPB, DWJ_TABLE_WORDS>(table, t, s_tab4);
+    grp::load_rows<TPB>(root_states, e0, ne, IN_ROOT, t, s_root);
+    grp::load_rows<TPB>(dof_state, e0, ne, IN_DOF, t, s_dof);
+    if (mass_scale != nullptr) grp::load_rows<TPB>(mass_scale, e0, ne, dwj::NB, t, s_ms);
+    if (dof_armature != nullptr) grp::load_rows<TPB>(dof_armature, e0, ne, DWJ_NUM_DOF, t, s_arm);
     __syncthreads();
     const dwb::Tab T{reinterpret_cast<const uint32_t *>(s_tab4)};
     const int nleaf = T.nleaf();
@@ -111,12 +111,12 @@ __global__ __launch_bounds__(TPB) void dwj_k_mass_matrix(int n, const uint4 *__r
     }
     __syncthreads();
     const bool arm = dof_armature != nullptr;
-    dwg::store_block<TPB>(mm + (size_t)e0 * dwj::MMW, ne * dwj::MMW, (reinterpret_cast<uintptr_t>(mm) & 15u) == 0u, t, [&](int idx) {
+    grp::store_block<TPB>(mm + (size_t)e0 * dwj::MMW, ne * dwj::MMW, (reinterpret_cast<uintptr_t>(mm) & 15u) == 0u, t, [&](int idx) {
         const int e = idx / dwj::MMW, w = idx - dwj::MMW * e, r = w / dwj::NV;
         return dwj::mm_word(T, s_env + e * dwj::MM_ENV, arm ? s_arm + e * DWJ_NUM_DOF : nullptr, r, w - dwj::NV * r);
     });
     if (com_jac != nullptr)
-        dwg::store_block<TPB>(com_jac + (size_t)e0 * dwj::CJW, ne * dwj::CJW, (reinterpret_cast<uintptr_t>(com_jac) & 15u) == 0u, t, [&](int idx) {
+        grp::store_block<TPB>(com_jac + (size_t)e0 * dwj::CJW, ne * dwj::CJW, (reinterpret_cast<uintptr_t>(com_jac) & 15u) == 0u, t, [&](int idx) {
             const int e = idx / dwj::CJW, w = idx - dwj::CJW * e, r = w / dwj::NV;
             return dwj::cj_word(T, s_env + e * dwj::MM_ENV, r, w - dwj::NV * r);
         });
@@ -156,8 +156,7 @@ int dwj_jacobian(int32_t num_envs, const uint32_t *table, const float *root_stat
     }
     hipLaunchKernelGGL(dwj_k_jacobian, dim3(dwj::groups(num_envs)), dim3(TPB), 0, (hipStream_t)stream, (int)num_envs,
                        reinterpret_cast<const uint4 *>(table), root_states, dof_state, ids, (int)nb, (int)(vel_at_com != 0), jac);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : s_err.fail_hip("dwj_jacobian: launch", e);
+    return s_err.launched("dwj_jacobian");
 }
 
 int dwj_mass_matrix(int32_t num_envs, const uint32_t *table, const float *root_states, const float *dof_state, const float *mass_scale,
@@ -165,8 +164,7 @@ int dwj_mass_matrix(int32_t num_envs, const uint32_t *table, const float *root_s
     if (check_common("dwj_mass_matrix", num_envs, table, root_states, dof_state, mm) != 0) return -1;
     hipLaunchKernelGGL(dwj_k_mass_matrix, dim3(dwj::groups(num_envs)), dim3(TPB), 0, (hipStream_t)stream, (int)num_envs,
                        reinterpret_cast<const uint4 *>(table), root_states, dof_state, mass_scale, dof_armature, (int)(vel_at_com != 0), mm, com_jac);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : s_err.fail_hip("dwj_mass_matrix: launch", e);
+    return s_err.launched("dwj_mass_matrix");
 }
 
 }  // extern "C"

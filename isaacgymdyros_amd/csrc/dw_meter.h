@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "../../include/dyros_meter.h"
+#include "dw_episode.h"
 
 #if defined(__HIPCC__)
 #define DWM_HD __host__ __device__ inline
@@ -21,8 +22,8 @@ static_assert(NW == 4, "a partial row is ((w0 + w1) + w2) + w3");
 static_assert(DWM_MS_MEAN + DWM_COLS_MAX == DWM_MS_MEAN_LEN && DWM_MS_GAMES % 2 == 0 && DWM_MS_DISCARDED % 2 == 0 && DWM_MS_SUM_RET % 2 == 0 &&
               DWM_MS_SUM_LEN % 2 == 0 && DWM_MS_SUM_LEN + 2 == DWM_MS_WORDS, "ms: the length's mean follows the columns'; 64-bit words are aligned");
 
-DWM_HD uint32_t f2u(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-DWM_HD float u2f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+using epi::f2u;
+using epi::u2f;
 DWM_HD bool finite(float x) { return (f2u(x) & 0x7f800000u) != 0x7f800000u; }
 
 DWM_HD int groups(int n) { return (n + GROUP - 1) / GROUP; }

@@ -8,16 +8,12 @@
 //                 increment.  The workgroup that draws the last ticket reads the partial rows past its L1, adds them in workgroup-index order
 //                 (64 rows per pass through LDS, one lane per column), updates ms and sets the ticket back to zero.  No workgroup waits.
 //   dwm_k_clear   zeroes ms and the head of work.
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-
+#include "dw_group.h"
 #include "dw_meter.h"
 
 namespace {
 
-char s_err[256] = "";
-int fail(const char *msg) { snprintf(s_err, sizeof(s_err), "%s", msg); return -1; }
-int fail_hip(const char *who, hipError_t e) { snprintf(s_err, sizeof(s_err), "%s: %s", who, hipGetErrorString(e)); return -1; }
+grp::Err s_err;
 
 using dwm::CMAX;
 using dwm::GROUP;
@@ -175,17 +171,11 @@ __global__ __launch_bounds__(WAVE) void dwm_k_clear(uint32_t *ms, uint32_t *work
     if (t < HEAD) work[t] = 0u;
 }
 
+#define DWM_STR_(x) #x
+#define DWM_STR(x) DWM_STR_(x)
 int check_shape(const char *who, int32_t num_envs, int32_t cols) {
-    static char msg[128];
-    if (num_envs < 1 || num_envs > 0x7fffffff - GROUP) {
-        snprintf(msg, sizeof(msg), "%s: num_envs must be in [1, 2^31 - %d)", who, GROUP);
-        return fail(msg);
-    }
-    if (cols < 1 || cols > DWM_COLS_MAX) {
-        snprintf(msg, sizeof(msg), "%s: cols must be in [1, %d]", who, DWM_COLS_MAX);
-        return fail(msg);
-    }
-    return 0;
+    if (s_err.envs(who, num_envs, GROUP) != 0) return -1;
+    return cols >= 1 && cols <= DWM_COLS_MAX ? 0 : s_err.fail(who, "cols must be in [1, " DWM_STR(DWM_COLS_MAX) "]");
 }
 
 }  // namespace
@@ -193,7 +183,7 @@ int check_shape(const char *who, int32_t num_envs, int32_t cols) {
 extern "C" {
 
 int dwm_abi_version(void) { return DWM_ABI_VERSION; }
-const char *dwm_last_error(void) { return s_err; }
+const char *dwm_last_error(void) { return s_err.s; }
 
 int64_t dwm_work_words(int32_t num_envs, int32_t cols) {
     if (check_shape("dwm_work_words", num_envs, cols) != 0) return -1;
@@ -203,22 +193,20 @@ int64_t dwm_work_words(int32_t num_envs, int32_t cols) {
 int dwm_record(int32_t num_envs, int32_t cols, int32_t max_size, const float *rew, const float *stacked, int32_t stacked_stride,
                const int64_t *done, float *cur, void *ms, void *work, void *stream) {
     if (check_shape("dwm_record", num_envs, cols) != 0) return -1;
-    if (max_size < 1) return fail("dwm_record: max_size must be positive");
-    if (!rew || !done || !cur || !ms || !work) return fail("dwm_record: a buffer is missing");
-    if (cols > 1 && !stacked) return fail("dwm_record: cols > 1 needs the stacked reward terms");
-    if (cols > 1 && stacked_stride < cols - 1) return fail("dwm_record: stacked_stride must be at least cols - 1");
-    if ((reinterpret_cast<uintptr_t>(ms) & 7u) != 0u) return fail("dwm_record: ms must be 8-byte aligned");
+    if (max_size < 1) return s_err.fail("dwm_record: max_size must be positive");
+    if (!rew || !done || !cur || !ms || !work) return s_err.fail("dwm_record: a buffer is missing");
+    if (cols > 1 && !stacked) return s_err.fail("dwm_record: cols > 1 needs the stacked reward terms");
+    if (cols > 1 && stacked_stride < cols - 1) return s_err.fail("dwm_record: stacked_stride must be at least cols - 1");
+    if ((reinterpret_cast<uintptr_t>(ms) & 7u) != 0u) return s_err.fail("dwm_record: ms must be 8-byte aligned");
     hipLaunchKernelGGL(dwm_k_record, dim3(dwm::groups(num_envs)), dim3(GROUP), 0, (hipStream_t)stream, (int)num_envs, (int)cols, (uint32_t)max_size,
                        rew, stacked, (int)stacked_stride, done, cur, (uint32_t *)ms, (uint32_t *)work);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dwm_record: launch", e);
+    return s_err.launched("dwm_record");
 }
 
 int dwm_clear(void *ms, void *work, void *stream) {
-    if (!ms || !work) return fail("dwm_clear: a buffer is missing");
+    if (!ms || !work) return s_err.fail("dwm_clear: a buffer is missing");
     hipLaunchKernelGGL(dwm_k_clear, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, (uint32_t *)ms, (uint32_t *)work);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dwm_clear: launch", e);
+    return s_err.launched("dwm_clear");
 }
 
 }  // extern "C"

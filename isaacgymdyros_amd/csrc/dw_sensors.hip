@@ -16,7 +16,7 @@
 
 namespace {
 
-dwg::Err s_err;
+grp::Err s_err;
 int fail(const char *msg) { return s_err.fail("dwf_refresh", msg); }
 
 constexpr int G = dwf::G, TPB = 256;
@@ -60,8 +60,8 @@ __global__ __launch_bounds__(TPB) void dwf_k_refresh(int n, const uint4 *__restr
     const int t = threadIdx.x, e0 = blockIdx.x * G;
     const int ne = n - e0 < G ? n - e0 : G;          // envs of this workgroup (the last one may hold fewer)
     // ---- loads: consecutive lanes, consecutive words ----
-    dwg::load_table<TPB, DWB_TABLE_WORDS>(table, t, s_tab4);
-    dwg::load_rows<TPB>(root_states, e0, ne, dwf::IN_ROOT, t, s_root);
+    grp::load_table<TPB, DWB_TABLE_WORDS>(table, t, s_tab4);
+    grp::load_rows<TPB>(root_states, e0, ne, dwf::IN_ROOT, t, s_root);
     {
         const float *src = dof_state + (size_t)e0 * DWF_DOF_ROW;
         for (int i = t; i < ne * dwf::IN_DOF; i += TPB) {
@@ -133,8 +133,7 @@ int dwf_refresh(int32_t num_envs, const uint32_t *table, const float *root_state
     hipLaunchKernelGGL(dwf_k_refresh, dim3(dwf::groups(num_envs)), dim3(TPB), 0, (hipStream_t)stream, (int)num_envs,
                        reinterpret_cast<const uint4 *>(table), root_states, dof_state, reinterpret_cast<const uint4 *>(env_state), *model_host, sen,
                        (int)ns, sensors, cop, zmp, corners);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : s_err.fail_hip("dwf_refresh: launch", e);
+    return s_err.launched("dwf_refresh");
 }
 
 }  // extern "C"

@@ -5,10 +5,10 @@
 
 #include <math.h>
 #include <stdint.h>
-#include <string.h>
 
 #include "../../include/dyros_walk.h"
 #include "../../include/dyros_stats.h"
+#include "dw_episode.h"
 
 #if defined(__HIPCC__)
 #define DWS_HD __host__ __device__ inline
@@ -20,26 +20,24 @@ namespace dws {
 
 constexpr int NB = DW_NUM_BODIES, ESW = DW_ES_WORDS;
 
-DWS_HD float u2f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-DWS_HD uint32_t f2u(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+using epi::f2u;
+using epi::partial;
+using epi::Rows;
+using epi::RT;
+using epi::u2f;
 
 // |F| > 1 N exactly as the step kernel's collision test forms it (dw_limb.h over_1n: torch.norm's order for three elements)
-DWS_HD bool over_1n(float x, float y, float z) {
-    float b = fmaf(x, x, 0.0f);
-    b = fmaf(y, y, b);
-    b = fmaf(z, z, b);
-    return sqrtf(b) > 1.0f;
-}
+struct Over1N {
+    DWS_HD bool operator()(float x, float y, float z) const {
+        float b = fmaf(x, x, 0.0f);
+        b = fmaf(y, y, b);
+        b = fmaf(z, z, b);
+        return sqrtf(b) > 1.0f;
+    }
+};
 
 // bit g of (lo | hi << 32): Gym body g (not a sole) is over 1 N
-DWS_HD void contact_mask(const float *cf, uint32_t &lo, uint32_t &hi) {
-    lo = hi = 0u;
-    for (int g = 0; g < NB; ++g)
-        if (g != DWS_LFOOT && g != DWS_RFOOT && over_1n(cf[3 * g], cf[3 * g + 1], cf[3 * g + 2])) {
-            if (g < 32) lo |= 1u << g;
-            else hi |= 1u << (g - 32);
-        }
-}
+DWS_HD void contact_mask(const float *cf, uint32_t &lo, uint32_t &hi) { epi::contact_mask<NB, DWS_LFOOT, DWS_RFOOT>(cf, lo, hi, Over1N{}); }
 
 // one env's words of the step's buffers
 struct EnvIn {
@@ -48,15 +46,6 @@ struct EnvIn {
     const float *tq;          // [12]     action_torque
     float tv0, tv1, tf0, tf1, last_return, total_mass;
     int pert_on, nan_resets, reset;
-};
-
-// SoA view of st / ac: word k of env e at k * n + e
-struct Rows {
-    uint32_t *st;
-    float *ac;
-    int n, e;
-    DWS_HD uint32_t &w(int k) const { return st[(size_t)k * n + e]; }
-    DWS_HD float &a(int k) const { return ac[(size_t)k * n + e]; }
 };
 
 // the running episode of one env (the DWS_ST_* words), held in registers between one load and one store: every global load of an update is
@@ -196,15 +185,6 @@ DWS_HD void count_call(uint64_t *ct, int env0_perturb_start) {
     if (env0_perturb_start && ct[DWS_CT_GATE_AT] == 0) ct[DWS_CT_GATE_AT] = call + 1;
     ct[DWS_CT_CALLS] = call + 1;
     ct[DWS_CT_RECORDS] += 1;
-}
-
-// the fixed order of every float sum of dws_summarize: RT partial sums in double over e = t, t + RT, ..., then a halving tree
-constexpr int RT = 256;
-
-DWS_HD double partial(const float *row, int n, int t) {
-    double s = 0.0;
-    for (int e = t; e < n; e += RT) s += (double)row[e];
-    return s;
 }
 
 }  // namespace dws

@@ -6,70 +6,37 @@
 //                counts gathered in LDS and added to ct with one atomic per non-zero word and workgroup.
 //   k_restart    one lane per listed env (or every env).
 //   k_summarize  one workgroup per float word of ac: every sum in dws's fixed order; the counts converted.
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-
+#include "dw_record_group.h"
 #include "dw_stats.h"
 
 namespace {
 
-char s_err[256] = "";
-int fail(const char *msg) { snprintf(s_err, sizeof(s_err), "%s", msg); return -1; }
-int fail_hip(const char *who, hipError_t e) { snprintf(s_err, sizeof(s_err), "%s: %s", who, hipGetErrorString(e)); return -1; }
+grp::Err s_err;
 
-// envs and lanes per workgroup: 32 / 128 measured fastest at 16384 envs against 16 / 128, 16 / 64, 8 / 128, 8 / 64, 4 / 64
-constexpr int EPB = 32, TPB = 128;
-constexpr int CFW = EPB * dws::NB * 3;              // contact words of a workgroup
-constexpr int TQW = 12;                             // action_torque
-static_assert(EPB <= TPB && TPB % 64 == 0, "one lane per env");
-static_assert((dws::NB * 3 * EPB) % 4 == 0, "a workgroup's contact span is whole 16-byte pieces");
-
-struct LdsCount {
-    unsigned int *w;
-    __device__ void add(int k, unsigned int v) const { if (v) atomicAdd(&w[k], v); }
-    __device__ void max(int k, unsigned int v) const { atomicMax(&w[k], v); }
-};
+using rec::EPB;
+using rec::TPB;
+constexpr int RTW = EPB * 13, TQW = 12;             // root words of a workgroup; action_torque words of an env
 
 __global__ __launch_bounds__(TPB) void dws_k_record(int n, const float *__restrict__ root_states, const float *__restrict__ contact_forces,
                                                     const float *__restrict__ env_state, const int64_t *__restrict__ reset_buf,
                                                     const float *__restrict__ total_mass, uint32_t *__restrict__ st, float *__restrict__ ac,
                                                     unsigned long long *ct, uint8_t *cause, float max_len, float dt_policy) {
-    __shared__ float4 s_cf4[CFW / 4];
-    __shared__ float s_root[EPB * 13];
+    __shared__ float4 s_cf4[rec::CFW / 4];
+    __shared__ float s_root[RTW];
     __shared__ float s_tq[EPB * TQW];
     __shared__ unsigned int s_mask[EPB][2];
     __shared__ unsigned int s_ct[DWS_CT_WINDOW];
     float *s_cf = reinterpret_cast<float *>(s_cf4);
     const int t = threadIdx.x, e0 = blockIdx.x * EPB;
     const int ne = n - e0 < EPB ? n - e0 : EPB;          // envs of this workgroup (the last one may hold fewer)
-    // ---- every global load first, into registers: the contact rows (one contiguous span of ne * 114 words from a 16-byte aligned start,
-    //      e0 * 456 B), the root rows, the torque words; and on lanes 0 .. ne - 1 the env's own words and its running state ----
-    constexpr int NCF = (CFW / 4 + TPB - 1) / TPB, NRT = (EPB * 13 + TPB - 1) / TPB, NTQ = (EPB * TQW + TPB - 1) / TPB;
-    const float *cf = contact_forces + (size_t)e0 * dws::NB * 3;
-    const int ncf = ne * dws::NB * 3;
-    float4 vcf[NCF];
-    float vrt[NRT], vtq[NTQ];
+    // ---- every global load first, into registers: the contact rows, the root rows, the torque words (a strided gather from env_state);
+    //      and on lanes 0 .. ne - 1 the env's own words and its running state ----
+    float4 vcf[rec::NCF];
+    float vrt[rec::regs(RTW)], vtq[rec::regs(EPB * TQW)];
+    rec::contact_load(vcf, contact_forces, e0, ne, t);
+    rec::span_load<RTW>(vrt, root_states + (size_t)e0 * 13, ne * 13, t);
 #pragma unroll
-    for (int k = 0; k < NCF; ++k) {
-        const int i = t + k * TPB;
-        if (ne == EPB) {
-            if (i < CFW / 4) vcf[k] = reinterpret_cast<const float4 *>(cf)[i];
-        } else {
-            float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (4 * i + 0 < ncf) v.x = cf[4 * i + 0];
-            if (4 * i + 1 < ncf) v.y = cf[4 * i + 1];
-            if (4 * i + 2 < ncf) v.z = cf[4 * i + 2];
-            if (4 * i + 3 < ncf) v.w = cf[4 * i + 3];
-            vcf[k] = v;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < NRT; ++k) {
-        const int i = t + k * TPB;
-        vrt[k] = i < ne * 13 ? root_states[(size_t)e0 * 13 + i] : 0.0f;
-    }
-#pragma unroll
-    for (int k = 0; k < NTQ; ++k) {
+    for (int k = 0; k < rec::regs(EPB * TQW); ++k) {
         const int i = t + k * TPB, el = i / TQW, w = i - TQW * el;
         vtq[k] = i < ne * TQW ? env_state[(size_t)(e0 + el) * dws::ESW + DW_ES_ACTION_TORQUE + w] : 0.0f;
     }
@@ -94,57 +61,33 @@ __global__ __launch_bounds__(TPB) void dws_k_record(int n, const float *__restri
         s = dws::load(r);
         h = dws::load_hot(r);
     }
-    // ---- into LDS; the bodies over 1 N as a bit mask per env (one lane per env and body) ----
-#pragma unroll
-    for (int k = 0; k < NCF; ++k) {
-        const int i = t + k * TPB;
-        if (i < CFW / 4) s_cf4[i] = vcf[k];
-    }
-#pragma unroll
-    for (int k = 0; k < NRT; ++k) {
-        const int i = t + k * TPB;
-        if (i < EPB * 13) s_root[i] = vrt[k];
-    }
-#pragma unroll
-    for (int k = 0; k < NTQ; ++k) {
-        const int i = t + k * TPB;
-        if (i < EPB * TQW) s_tq[i] = vtq[k];
-    }
-    for (int i = t; i < EPB * 2; i += TPB) s_mask[i >> 1][i & 1] = 0u;
-    for (int i = t; i < DWS_CT_WINDOW; i += TPB) s_ct[i] = 0u;
+    // ---- into LDS; the bodies over 1 N as a bit mask per env ----
+    rec::contact_store(s_cf4, vcf, t);
+    rec::span_store<RTW>(s_root, vrt, t);
+    rec::span_store<EPB * TQW>(s_tq, vtq, t);
+    rec::zero_counts<DWS_CT_WINDOW>(s_mask, s_ct, t);
     __syncthreads();
-    for (int i = t; i < ne * dws::NB; i += TPB) {
-        const int el = i / dws::NB, g = i - dws::NB * el;
-        const float *f = s_cf + 3 * i;
-        if (g != DWS_LFOOT && g != DWS_RFOOT && dws::over_1n(f[0], f[1], f[2])) atomicOr(&s_mask[el][g >> 5], 1u << (g & 31));
-    }
+    rec::mask_pass<DWS_LFOOT, DWS_RFOOT>(s_cf, s_mask, ne, t, dws::Over1N{});
     __syncthreads();
     // ---- one lane per env ----
     if (own) {
         in.cf = s_cf + t * dws::NB * 3;
         in.root = s_root + t * 13;
         in.tq = s_tq + t * TQW;
-        LdsCount c{s_ct};
+        rec::LdsCount c{s_ct};
         cause[e] = (uint8_t)dws::update(in, s_mask[t][0], s_mask[t][1], s, h, r, c, max_len, dt_policy);
         dws::store(r, s);
         dws::store_hot(r, h);
     }
     if (blockIdx.x == 0 && t == 0) dws::count_call(reinterpret_cast<uint64_t *>(ct), reinterpret_cast<const int *>(env_state)[DW_ES_PERT_START]);
     __syncthreads();
-    for (int i = t; i < DWS_CT_WINDOW; i += TPB) {
-        const unsigned int v = s_ct[i];
-        if (v == 0u || i == DWS_CT_RECORDS) continue;
-        if (i == DWS_CT_LEN_MAX) atomicMax(&ct[i], (unsigned long long)v);
-        else atomicAdd(&ct[i], (unsigned long long)v);
-    }
+    rec::flush<DWS_CT_WINDOW, DWS_CT_RECORDS, DWS_CT_LEN_MAX>(s_ct, ct, t);
 }
 
 __global__ __launch_bounds__(256) void dws_k_restart(int n, const int32_t *__restrict__ ids, int num_ids, const float *__restrict__ root_states,
                                                      const float *__restrict__ env_state, const int64_t *__restrict__ progress_buf, uint32_t *st) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= num_ids) return;
-    const int e = ids ? ids[i] : i;
-    if (e < 0 || e >= n) return;
+    int e;
+    if (!grp::listed_env(ids, num_ids, n, e)) return;
     const float *es = env_state + (size_t)e * dws::ESW;
     const int *esi = reinterpret_cast<const int *>(es);
     dws::St s;
@@ -152,19 +95,8 @@ __global__ __launch_bounds__(256) void dws_k_restart(int n, const int32_t *__res
     dws::store(dws::Rows{st, nullptr, n, e}, s);
 }
 
-// one workgroup per float word of ac (word blockIdx.x); workgroup 0 also converts the counts
 __global__ __launch_bounds__(dws::RT) void dws_k_summarize(int n, const float *__restrict__ ac, const unsigned long long *__restrict__ ct, double *out) {
-    __shared__ double red[dws::RT];
-    const int t = threadIdx.x, k = blockIdx.x;
-    if (k == 0)
-        for (int i = t; i < DWS_CT_WORDS; i += dws::RT) out[i] = (double)ct[i];
-    red[t] = dws::partial(ac + (size_t)k * n, n, t);
-    __syncthreads();
-    for (int s = dws::RT / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    if (t == 0) out[DWS_SUM_AC + k] = red[0];
+    rec::summarize<DWS_CT_WORDS, DWS_SUM_AC>(n, ac, ct, out);
 }
 
 }  // namespace
@@ -172,41 +104,37 @@ __global__ __launch_bounds__(dws::RT) void dws_k_summarize(int n, const float *_
 extern "C" {
 
 int dws_abi_version(void) { return DWS_ABI_VERSION; }
-const char *dws_last_error(void) { return s_err; }
+const char *dws_last_error(void) { return s_err.s; }
 
 int dws_record(int32_t num_envs, const float *root_states, const float *contact_forces, const float *env_state, const int64_t *reset_buf,
                const float *total_mass, void *st, float *ac, uint64_t *ct, uint8_t *cause, float max_episode_length, float dt_policy,
                void *stream) {
-    if (num_envs < 1) return fail("dws_record: num_envs must be positive");
+    if (num_envs < 1) return s_err.fail("dws_record: num_envs must be positive");
     if (!root_states || !contact_forces || !env_state || !reset_buf || !total_mass || !st || !ac || !ct || !cause)
-        return fail("dws_record: a buffer is missing");
-    if (!(max_episode_length > 0.0f)) return fail("dws_record: max_episode_length must be positive");
-    if ((reinterpret_cast<uintptr_t>(contact_forces) & 15u) != 0u) return fail("dws_record: contact_forces must be 16-byte aligned");
+        return s_err.fail("dws_record: a buffer is missing");
+    if (!(max_episode_length > 0.0f)) return s_err.fail("dws_record: max_episode_length must be positive");
+    if ((reinterpret_cast<uintptr_t>(contact_forces) & 15u) != 0u) return s_err.fail("dws_record: contact_forces must be 16-byte aligned");
     hipLaunchKernelGGL(dws_k_record, dim3((num_envs + EPB - 1) / EPB), dim3(TPB), 0, (hipStream_t)stream, (int)num_envs, root_states, contact_forces,
                        env_state, reset_buf, total_mass, (uint32_t *)st, ac, (unsigned long long *)ct, cause, max_episode_length, dt_policy);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dws_record: launch", e);
+    return s_err.launched("dws_record");
 }
 
 int dws_restart(int32_t num_envs, const int32_t *env_ids, int32_t num_ids, const float *root_states, const float *env_state,
                 const int64_t *progress_buf, void *st, void *stream) {
-    if (num_envs < 1) return fail("dws_restart: num_envs must be positive");
-    if (!root_states || !env_state || !progress_buf || !st) return fail("dws_restart: a buffer is missing");
-    const int m = env_ids ? num_ids : num_envs;
-    if (m < 0 || (env_ids && num_ids > num_envs)) return fail("dws_restart: bad env id list");
-    if (m == 0) return 0;
+    if (num_envs < 1) return s_err.fail("dws_restart: num_envs must be positive");
+    if (!root_states || !env_state || !progress_buf || !st) return s_err.fail("dws_restart: a buffer is missing");
+    const int m = s_err.listed("dws_restart", env_ids, num_ids, num_envs, num_envs);
+    if (m <= 0) return m;
     hipLaunchKernelGGL(dws_k_restart, dim3((m + 255) / 256), dim3(256), 0, (hipStream_t)stream, (int)num_envs, env_ids, m, root_states, env_state,
                        progress_buf, (uint32_t *)st);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dws_restart: launch", e);
+    return s_err.launched("dws_restart");
 }
 
 int dws_summarize(int32_t num_envs, const float *ac, const uint64_t *ct, double *out, void *stream) {
-    if (num_envs < 1) return fail("dws_summarize: num_envs must be positive");
-    if (!ac || !ct || !out) return fail("dws_summarize: a buffer is missing");
+    if (num_envs < 1) return s_err.fail("dws_summarize: num_envs must be positive");
+    if (!ac || !ct || !out) return s_err.fail("dws_summarize: a buffer is missing");
     hipLaunchKernelGGL(dws_k_summarize, dim3(DWS_AC_WORDS), dim3(dws::RT), 0, (hipStream_t)stream, (int)num_envs, ac, (const unsigned long long *)ct, out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dws_summarize: launch", e);
+    return s_err.launched("dws_summarize");
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@
 #include "../../include/dyros_walk.h"
 #include "../../include/dyros_stats.h"
 #include "../../include/dyros_trace.h"
+#include "dw_episode.h"
 
 #if defined(__HIPCC__)
 #define DWT_HD __host__ __device__ inline
@@ -21,8 +22,8 @@ namespace dwt {
 
 constexpr int NB = DW_NUM_BODIES, ESW = DW_ES_WORDS, ROW = DWT_ROW_WORDS, CFW = DW_NUM_BODIES * 3;
 
-DWT_HD float u2f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-DWT_HD uint32_t f2u(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+using epi::f2u;
+using epi::u2f;
 
 // The source spans of a row's float words.  Word i of a span (0 <= i < len) comes from word src + i of the env's row of buffer `buf` and
 // goes to row word dst_of(span, i): consecutive i are consecutive source words, and -- but for the de-interleave of dof_state --

@@ -7,16 +7,12 @@
 //                 reduction, and the row leaves as 52 16-byte stores of consecutive lanes.  Plain stores, no atomics: one wave owns a slot.
 //   dwt_k_arm     one lane per listed env (or every env).
 //   dwt_k_gather  one wavefront per output row, the same 16 bytes per lane.
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-
+#include "dw_group.h"
 #include "dw_trace.h"
 
 namespace {
 
-char s_err[256] = "";
-int fail(const char *msg) { snprintf(s_err, sizeof(s_err), "%s", msg); return -1; }
-int fail_hip(const char *who, hipError_t e) { snprintf(s_err, sizeof(s_err), "%s: %s", who, hipGetErrorString(e)); return -1; }
+grp::Err s_err;
 
 constexpr int WAVE = 64, SPB = 4, TPB = SPB * WAVE;          // slots (wavefronts) and lanes per workgroup
 constexpr int ROW4 = dwt::ROW / 4;                            // 16-byte pieces of a row
@@ -99,10 +95,8 @@ __global__ __launch_bounds__(TPB) void dwt_k_record(int n, int k, int depth, int
 
 __global__ __launch_bounds__(256) void dwt_k_arm(int n, int k, const int32_t *__restrict__ ids, int num_ids, const int64_t *__restrict__ progress_buf,
                                                  const int32_t *__restrict__ env_slot, uint32_t *ss) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= num_ids) return;
-    const int e = ids ? ids[i] : i;
-    if (e < 0 || e >= n) return;
+    int e;
+    if (!grp::listed_env(ids, num_ids, n, e)) return;
     const int s = env_slot[e];
     if (s < 0 || s >= k) return;
     dwt::Slot t;
@@ -132,56 +126,52 @@ __global__ __launch_bounds__(TPB) void dwt_k_gather(int k, int depth, const int3
 extern "C" {
 
 int dwt_abi_version(void) { return DWT_ABI_VERSION; }
-const char *dwt_last_error(void) { return s_err; }
+const char *dwt_last_error(void) { return s_err.s; }
 
 int dwt_record(int32_t num_envs, int32_t num_slots, int32_t depth, int32_t hold_mode, const int32_t *slot_env, const float *root_states,
                const float *dof_state, const float *contact_forces, const float *env_state, const float *rew_buf,
                const float *stacked_rewards, const int64_t *reset_buf, const int64_t *timeout_buf, float max_episode_length, void *ss,
                void *ring, void *stream) {
-    if (num_envs < 1) return fail("dwt_record: num_envs must be positive");
-    if (num_slots < 1 || num_slots > num_envs) return fail("dwt_record: num_slots must be in [1, num_envs]");
-    if (depth < 1) return fail("dwt_record: depth must be positive");
-    if (hold_mode != DWT_HOLD_NEVER && hold_mode != DWT_HOLD_FALL && hold_mode != DWT_HOLD_RESET) return fail("dwt_record: unknown hold mode");
+    if (num_envs < 1) return s_err.fail("dwt_record: num_envs must be positive");
+    if (num_slots < 1 || num_slots > num_envs) return s_err.fail("dwt_record: num_slots must be in [1, num_envs]");
+    if (depth < 1) return s_err.fail("dwt_record: depth must be positive");
+    if (hold_mode != DWT_HOLD_NEVER && hold_mode != DWT_HOLD_FALL && hold_mode != DWT_HOLD_RESET) return s_err.fail("dwt_record: unknown hold mode");
     if (!slot_env || !root_states || !dof_state || !contact_forces || !env_state || !rew_buf || !stacked_rewards || !reset_buf || !timeout_buf ||
         !ss || !ring)
-        return fail("dwt_record: a buffer is missing");
-    if (!(max_episode_length > 0.0f)) return fail("dwt_record: max_episode_length must be positive");
-    if ((reinterpret_cast<uintptr_t>(ring) & 15u) != 0u) return fail("dwt_record: ring must be 16-byte aligned");
+        return s_err.fail("dwt_record: a buffer is missing");
+    if (!(max_episode_length > 0.0f)) return s_err.fail("dwt_record: max_episode_length must be positive");
+    if ((reinterpret_cast<uintptr_t>(ring) & 15u) != 0u) return s_err.fail("dwt_record: ring must be 16-byte aligned");
     hipLaunchKernelGGL(dwt_k_record, dim3((num_slots + SPB - 1) / SPB), dim3(TPB), 0, (hipStream_t)stream, (int)num_envs, (int)num_slots, (int)depth,
                        (int)hold_mode, slot_env, root_states, dof_state, contact_forces, env_state, rew_buf, stacked_rewards, reset_buf, timeout_buf,
                        max_episode_length, (uint32_t *)ss, (float4 *)ring);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dwt_record: launch", e);
+    return s_err.launched("dwt_record");
 }
 
 int dwt_arm(int32_t num_envs, int32_t num_slots, const int32_t *env_ids, int32_t num_ids, const int64_t *progress_buf,
             const int32_t *env_slot, void *ss, void *stream) {
-    if (num_envs < 1) return fail("dwt_arm: num_envs must be positive");
-    if (num_slots < 1 || num_slots > num_envs) return fail("dwt_arm: num_slots must be in [1, num_envs]");
-    if (!progress_buf || !env_slot || !ss) return fail("dwt_arm: a buffer is missing");
-    const int m = env_ids ? num_ids : num_envs;
-    if (m < 0) return fail("dwt_arm: bad env id list");
-    if (m == 0) return 0;
+    if (num_envs < 1) return s_err.fail("dwt_arm: num_envs must be positive");
+    if (num_slots < 1 || num_slots > num_envs) return s_err.fail("dwt_arm: num_slots must be in [1, num_envs]");
+    if (!progress_buf || !env_slot || !ss) return s_err.fail("dwt_arm: a buffer is missing");
+    const int m = s_err.listed("dwt_arm", env_ids, num_ids, num_envs, INT32_MAX);
+    if (m <= 0) return m;
     hipLaunchKernelGGL(dwt_k_arm, dim3((m + 255) / 256), dim3(256), 0, (hipStream_t)stream, (int)num_envs, (int)num_slots, env_ids, m, progress_buf,
                        env_slot, (uint32_t *)ss);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dwt_arm: launch", e);
+    return s_err.launched("dwt_arm");
 }
 
 int dwt_gather(int32_t num_slots, int32_t depth, const int32_t *slot_ids, int32_t num_ids, const void *ss, const void *ring, void *out,
                int32_t *out_rows, void *stream) {
-    if (num_slots < 1) return fail("dwt_gather: num_slots must be positive");
-    if (depth < 1) return fail("dwt_gather: depth must be positive");
-    if (num_ids < 0 || (!slot_ids && num_ids > num_slots)) return fail("dwt_gather: bad slot id list");
-    if (!ss || !ring || !out || !out_rows) return fail("dwt_gather: a buffer is missing");
-    if (((reinterpret_cast<uintptr_t>(ring) | reinterpret_cast<uintptr_t>(out)) & 15u) != 0u) return fail("dwt_gather: ring and out must be 16-byte aligned");
-    if ((int64_t)num_ids * depth > 0x7fffffff - SPB) return fail("dwt_gather: num_ids * depth is too large");
+    if (num_slots < 1) return s_err.fail("dwt_gather: num_slots must be positive");
+    if (depth < 1) return s_err.fail("dwt_gather: depth must be positive");
+    if (num_ids < 0 || (!slot_ids && num_ids > num_slots)) return s_err.fail("dwt_gather: bad slot id list");
+    if (!ss || !ring || !out || !out_rows) return s_err.fail("dwt_gather: a buffer is missing");
+    if (((reinterpret_cast<uintptr_t>(ring) | reinterpret_cast<uintptr_t>(out)) & 15u) != 0u) return s_err.fail("dwt_gather: ring and out must be 16-byte aligned");
+    if ((int64_t)num_ids * depth > 0x7fffffff - SPB) return s_err.fail("dwt_gather: num_ids * depth is too large");
     if (num_ids == 0) return 0;
     const int rows = num_ids * depth;
     hipLaunchKernelGGL(dwt_k_gather, dim3((rows + SPB - 1) / SPB), dim3(TPB), 0, (hipStream_t)stream, (int)num_slots, (int)depth, slot_ids, (int)num_ids,
                        (const uint32_t *)ss, (const float4 *)ring, (float4 *)out, out_rows);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip("dwt_gather: launch", e);
+    return s_err.launched("dwt_gather");
 }
 
 }  // extern "C"

@@ -15,7 +15,7 @@ from typing import Any, Dict
 import numpy as np
 import torch
 
-from . import _lib, abi, model_tensors
+from . import _lib, abi, model_tensors, recorders
 from .model import NUM_BODIES, NUM_DOF, load_model
 from .task_constants import REWARD_NAMES, load_task_constants
 from .vec_task import VecTask
@@ -96,28 +96,9 @@ class DyrosDynamicWalk(VecTask):
         self._bound_obs = self._buf["obs_buf"]
         self._fresh_obs = (not self.alias_obs) and np.isinf(self.clip_obs)
         self.extras["reward_names"] = list(REWARD_NAMES)
-        # cfg sim.mi355.episode_stats: termination causes and per-episode statistics on the device, one launch after every step
-        # (isaacgymdyros_amd/episode_stats.py); off: None, and step() makes no extra launch
-        self.episode_stats = None
-        if self.cfg["sim"].get("mi355", {}).get("episode_stats", False):
-            from .episode_stats import EpisodeStats
-            self.episode_stats = EpisodeStats(self)
-            self.extras["termination_cause"] = self.episode_stats.cause
-        # cfg sim.mi355.run_trace: a ring of the last steps of chosen envs on the device, one launch after every step, optionally frozen at
-        # a fall (isaacgymdyros_amd/run_trace.py); off: None, and step() makes no extra launch
-        self.run_trace = None
-        spec = self.cfg["sim"].get("mi355", {}).get("run_trace")
-        if spec is not None and spec is not False:          # (as validate_cfg reads it: {} is the default trace)
-            from .run_trace import RunTrace
-            self.run_trace = RunTrace(self, spec)
-        # cfg sim.mi355.gait_profile: sole forces, contacts, the paid foot_contact_reward and the leg joints' tracking binned by mocap phase on
-        # the device, one launch after every step (isaacgymdyros_amd/gait_profile.py); off: None, and step() makes no
-        # extra launch
-        self.gait_profile = None
-        spec = self.cfg["sim"].get("mi355", {}).get("gait_profile")
-        if spec is not None and spec is not False:
-            from .gait_profile import GaitProfile
-            self.gait_profile = GaitProfile(self, spec)
+        # cfg sim.mi355.episode_stats, run_trace, gait_profile: the recorders, one launch each after every step (isaacgymdyros_amd/recorders.py's
+        # table, DESIGN.md sections 16, 18, 20); off: None, and step() makes no extra launch
+        recorders.attach(self, self.cfg["sim"].get("mi355", {}))
         # cfg sim.mi355.body_states, force_sensors, jacobians, dynamics, forward_dynamics, contact_dynamics, contact_inverse_dynamics, stance_inverse_dynamics, inverse_kinematics, height_scan: the model tensors, one launch per
         # refresh or call (isaacgymdyros_amd/model_tensors.py's tables, DESIGN.md sections 21-30); off: None, no buffer, and step() makes no
         # extra launch
@@ -392,13 +373,8 @@ class DyrosDynamicWalk(VecTask):
             log = torch.empty(self.num_envs, self._buf["stacked_rewards"].shape[1] + nc, device=self._tdev, dtype=torch.float)
             _lib.check(self._api, self._api["terrain_log"](self._h, log.data_ptr(), stream))
             self.extras["stacked_rewards"] = log
-        if self.episode_stats is not None:
-            self.episode_stats.record()          # (fills extras["termination_cause"] in place)
+        recorders.record_all(self)          # (the statistics fill extras["termination_cause"] in place)
         model_tensors.refresh_auto(self)
-        if self.run_trace is not None:
-            self.run_trace.record()
-        if self.gait_profile is not None:
-            self.gait_profile.record()
         self.obs_dict["obs"] = (self.obs_buf if fresh else self._clip_obs(self.obs_buf)).to(self.rl_device)
         return self.obs_dict, self.rew_buf.to(self.rl_device), self.reset_buf.to(self.rl_device), self.extras
 
@@ -409,10 +385,7 @@ class DyrosDynamicWalk(VecTask):
         nz = noise.data_ptr() if noise is not None else 0
         stream = torch.cuda.current_stream(self._tdev).cuda_stream
         _lib.check(self._api, self._api["reset_idx"](self._h, ids.data_ptr(), int(ids.numel()), nz, self._current_step(), stream))
-        if self.episode_stats is not None:
-            self.episode_stats.restart(ids)          # (the running episodes of these envs are discarded, not counted)
-        if self.run_trace is not None:
-            self.run_trace.arm(ids)
+        recorders.restart_all(self, ids)
         model_tensors.refresh_auto(self)
         # (reset_idx does not touch the observations: the reference recomputes them in the next step's post-physics, :655-669)
 
@@ -525,10 +498,7 @@ class DyrosDynamicWalk(VecTask):
         self._step_count = int(d["_step_count"])
         if self._step_dev is not None:
             self._step_dev.fill_(self._step_count)
-        if self.episode_stats is not None:
-            self.episode_stats.restart()
-        if self.run_trace is not None:
-            self.run_trace.arm()
+        recorders.restart_all(self)
 
     def close(self):
         if getattr(self, "_h", None) is not None:

@@ -17,9 +17,9 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, cbind
-from .cbind import check as _check
+from . import cbind
 from .ppo_update import _req
+from .recorders import EpisodeWindow, Window, div
 
 K = cbind.constants("dyros_stats.h", "dws_")
 K["DWS_SUM_AC"] = K["DWS_CT_WORDS"]                                  # (defined by expression in the header)
@@ -33,103 +33,70 @@ def declare(lib) -> dict:
     return cbind.declare(lib, "dyros_stats.h", "dws_")
 
 
+def validate(spec, num_envs=None) -> None:
+    """cfg sim.mi355.episode_stats (config.validate_cfg): a bool."""
+    if not isinstance(spec, bool):
+        raise ValueError("sim.mi355.episode_stats must be True or False")
+
+
 def fold(out, num_envs: int, max_episode_length: float, body_names) -> dict:
     """The summary dict from dws_summarize's [DWS_SUM_WORDS] doubles (a sequence of Python floats)."""
-    k = K
-    ct = lambda i: int(out[i])                                   # noqa: E731
-    ac = lambda i: float(out[k["DWS_SUM_AC"] + i])               # noqa: E731
-    eps = ct(k["DWS_CT_EPISODES"])
-    records = ct(k["DWS_CT_RECORDS"])
-    env_steps = records * num_envs
-    div = lambda a, b: a / b if b else float("nan")              # noqa: E731
-    causes = {CAUSES[c]: ct(k["DWS_CT_CAUSE"] + c) for c in range(1, 5)}
-    bodies = {body_names[g]: ct(k["DWS_CT_BODY"] + g) for g in range(len(body_names))}
+    w = Window(out, K, "DWS_")
+    ct, ac = w.ct, w.ac
+    s = w.head({CAUSES[c]: ct("CAUSE", c) for c in range(1, 5)}, body_names, max_episode_length)
+    eps, env_steps = s["episodes"], s["records"] * num_envs
     bins = []
-    for b in range(k["DWS_CMD_BINS"]):
-        ne, nr, nq = ct(k["DWS_CT_BIN_EP"] + b), ct(k["DWS_CT_BIN_ROOT"] + b), ct(k["DWS_CT_BIN_RATIO"] + b)
-        bins.append(dict(lo=CMD_EDGES[b], hi=CMD_EDGES[b + 1], episodes=ne, vel_error=div(ac(k["DWS_AC_VERR"] + b), nr),
-                         lateral_drift=div(ac(k["DWS_AC_DRIFT"] + b), nr), distance_ratio=div(ac(k["DWS_AC_RATIO"] + b), nq),
-                         ratio_episodes=nq))
-    gate_at = ct(k["DWS_CT_GATE_AT"])
-    return dict(
-        records=records, episodes=eps, causes=causes,
-        cause_fractions={n: div(v, eps) for n, v in causes.items()},
-        contact_bodies={n: v for n, v in bodies.items() if v},
-        mean_length=div(ct(k["DWS_CT_LEN_SUM"]), eps), max_length=ct(k["DWS_CT_LEN_MAX"]),
-        length_hist=[ct(k["DWS_CT_LEN_HIST"] + i) for i in range(k["DWS_LEN_BINS"])],
-        length_edges=[max_episode_length * i / k["DWS_LEN_BINS"] for i in range(k["DWS_LEN_BINS"] + 1)],
-        mean_return=div(ac(k["DWS_AC_RET"]), eps),
+    for b in range(K["DWS_CMD_BINS"]):
+        ne, nr, nq = ct("BIN_EP", b), ct("BIN_ROOT", b), ct("BIN_RATIO", b)
+        bins.append(dict(lo=CMD_EDGES[b], hi=CMD_EDGES[b + 1], episodes=ne, vel_error=div(ac("VERR", b), nr),
+                         lateral_drift=div(ac("DRIFT", b), nr), distance_ratio=div(ac("RATIO", b), nq), ratio_episodes=nq))
+    gate_at = ct("GATE_AT")
+    s.update(
         command_bins=bins,
-        sole_peak_mean=[div(ac(k["DWS_AC_PK"] + f), eps) for f in range(2)],
-        sole_over_1400=[div(ct(k["DWS_CT_PK_OVER"] + f), eps) for f in range(2)],
-        force_tracking_error=[div(ac(k["DWS_AC_FT"] + f), env_steps) for f in range(2)],
-        torque_mean=div(ac(k["DWS_AC_TAU"]), 12 * env_steps),
-        torque_diff_max_mean=div(ac(k["DWS_AC_DTM"]), eps),
-        pushes=ct(k["DWS_CT_PUSHES"]), push_falls=ct(k["DWS_CT_PUSH_FALLS"]),
-        perturb_start_latched=gate_at > 0, perturb_start_at_record=gate_at - 1 if gate_at else None,
-        record_calls=ct(k["DWS_CT_CALLS"]))
+        sole_over_1400=[div(ct("PK_OVER", f), eps) for f in range(2)],
+        force_tracking_error=[div(ac("FT", f), env_steps) for f in range(2)],
+        torque_mean=div(ac("TAU"), 12 * env_steps),
+        torque_diff_max_mean=div(ac("DTM"), eps),
+        pushes=ct("PUSHES"), push_falls=ct("PUSH_FALLS"),
+        perturb_start_latched=gate_at > 0, perturb_start_at_record=gate_at - 1 if gate_at else None)
+    return s
 
 
-class EpisodeStats:
+class EpisodeStats(EpisodeWindow):
     """The statistics of one DyrosDynamicWalk env (see the module docstring).  Buffers are allocated here, once."""
 
     CAUSES = CAUSES
 
-    def __init__(self, env):
-        self.api = declare(_lib.load()[0])
-        self.env = env
-        N, dev = env.num_envs, env._tdev
-        self.num_envs = N
-        self.st = torch.zeros(K["DWS_ST_WORDS"], N, dtype=torch.int32, device=dev)
-        self.ac = torch.zeros(K["DWS_AC_WORDS"], N, dtype=torch.float32, device=dev)
-        self.ct = torch.zeros(K["DWS_CT_WORDS"], dtype=torch.int64, device=dev)          # (uint64 on the device side)
-        self.cause = torch.zeros(N, dtype=torch.uint8, device=dev)
-        self.out = torch.zeros(K["DWS_SUM_WORDS"], dtype=torch.float64, device=dev)
+    def __init__(self, env, spec=True):
+        super().__init__(env, declare, K, "DWS_")
         self.body_names = list(env.model.body_names)          # (Gym rows: 8 and 16 are L_Foot_Link / R_Foot_Link)
         self.restart()
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.env._tdev).cuda_stream
-
     def _bufs(self):
-        b, N = self.env._buf, self.num_envs
-        return (_req("root_states", b["root_states"], torch.float32, shape=(N, 13)),
-                _req("contact_forces", b["contact_forces"], torch.float32, shape=(N, self.env.num_bodies, 3)),
-                _req("env_state", b["env_state"], torch.float32, numel=N * b["env_state"].shape[1]))
+        N, f = self.num_envs, torch.float32
+        return (self._in("root_states", f, shape=(N, 13)), self._in("contact_forces", f, shape=(N, self.env.num_bodies, 3)),
+                self._in("env_state", f, numel=N * self.env._buf["env_state"].shape[1]))
 
     def record(self):
         """After a step, on the step's stream (DyrosDynamicWalk.step calls it)."""
-        b, N = self.env._buf, self.num_envs
+        N = self.num_envs
         root, cf, es = self._bufs()
-        rb = _req("reset_buf", b["reset_buf"], torch.int64, shape=(N,))
-        tm = _req("total_mass", b["total_mass"], torch.float32, numel=N)
-        _check(self.api, self.api["record"](N, root.data_ptr(), cf.data_ptr(), es.data_ptr(), rb.data_ptr(), tm.data_ptr(), self.st.data_ptr(),
-                                            self.ac.data_ptr(), self.ct.data_ptr(), self.cause.data_ptr(), float(self.env.max_episode_length),
-                                            float(self.env.dt_policy), self._stream()))
+        self._launch("record", (N, root, cf, es, self._in("reset_buf", torch.int64, shape=(N,)), self._in("total_mass", torch.float32, numel=N),
+                                self.st.data_ptr(), self.ac.data_ptr(), self.ct.data_ptr(), self.cause.data_ptr(),
+                                float(self.env.max_episode_length), float(self.env.dt_policy)))
 
     def restart(self, env_ids: torch.Tensor = None):
         """Discards the running episode of env_ids (None: every env); their counters restart from progress_buf."""
-        b, N = self.env._buf, self.num_envs
+        N = self.num_envs
         root, _cf, es = self._bufs()
-        pb = _req("progress_buf", b["progress_buf"], torch.int64, shape=(N,))
         ids, n = None, N
         if env_ids is not None:
             ids = _req("env_ids", env_ids, torch.int32)
             n = ids.numel()
             if n == 0:
                 return
-        _check(self.api, self.api["restart"](N, ids.data_ptr() if ids is not None else None, n, root.data_ptr(), es.data_ptr(), pb.data_ptr(),
-                                             self.st.data_ptr(), self._stream()))
-
-    def reset_totals(self):
-        """Starts a new window."""
-        self.ac.zero_()
-        self.ct[:K["DWS_CT_WINDOW"]].zero_()
-
-    def raw(self) -> list:
-        """dws_summarize's doubles (one launch, one device-to-host copy)."""
-        _check(self.api, self.api["summarize"](self.num_envs, self.ac.data_ptr(), self.ct.data_ptr(), self.out.data_ptr(), self._stream()))
-        return self.out.cpu().tolist()
+        self._launch("restart", (N, ids.data_ptr() if ids is not None else None, n, root, es, self._in("progress_buf", torch.int64, shape=(N,)),
+                                 self.st.data_ptr()))
 
     def summary(self) -> dict:
         return fold(self.raw(), self.num_envs, float(self.env.max_episode_length), self.body_names)

@@ -23,6 +23,7 @@ import os
 import numpy as np
 
 from . import cbind
+from .recorders import Recorder
 
 K = cbind.constants("dyros_gait.h", "dwg_")
 EXPORTS = list(cbind.signatures("dyros_gait.h", "dwg_"))
@@ -86,7 +87,7 @@ def resolve(spec) -> dict:
     return out
 
 
-def validate(spec) -> None:
+def validate(spec, num_envs=None) -> None:
     """Range checks of cfg sim.mi355.gait_profile (config.validate_cfg)."""
     resolve(spec)
 
@@ -200,20 +201,17 @@ def format_line(s: dict) -> str:
                                 for n, w in s["windows"].items()) + "  (%d env-steps)" % s["recorded"]
 
 
-class GaitProfile:
+class GaitProfile(Recorder):
     """The gait profile of one DyrosDynamicWalk env (see the module docstring).  Buffers are allocated here, once."""
 
     def __init__(self, env, spec=True):
         import torch
-        from . import _lib
-        from .ppo_update import _req
         spec = resolve(spec)
         if spec is None:
             raise ValueError("GaitProfile: the spec switches the profile off")
-        self.api = declare(_lib.load()[0])
-        self.env = env
-        N, dev = env.num_envs, env._tdev
-        self.num_envs, self.bins = N, spec["bins"]
+        super().__init__(env, declare)
+        N, dev = self.num_envs, self._tdev
+        self.bins = spec["bins"]
         self.min_episode_step, self.skip_pushes = spec["min_episode_step"], spec["skip_pushes"]
         self.groups = self.api["groups"](N)
         if self.groups < 0:
@@ -221,32 +219,24 @@ class GaitProfile:
         self.part = torch.zeros(self.groups, self.bins, W, dtype=torch.int64, device=dev)
         self.ct = torch.zeros(K["DWG_CT_WORDS"], dtype=torch.int64, device=dev)
         self.out = torch.zeros(self.bins * W + K["DWG_CT_WORDS"], dtype=torch.int64, device=dev)
-        # dwg_record's arguments, checked once: no argument changes from call to call (the env's buffers are bound once)
-        b = env._buf
-        p = lambda name, dt, **kw: _req(name, b[name], dt, **kw).data_ptr()          # noqa: E731
+        p, f, i64 = self._in, torch.float32, torch.int64
         self._record_args = (
-            N, self.bins, self.min_episode_step, int(self.skip_pushes), p("root_states", torch.float32, shape=(N, 13)),
-            p("dof_state", torch.float32, numel=N * 66), p("contact_forces", torch.float32, shape=(N, env.num_bodies, 3)),
-            p("env_state", torch.float32, numel=N * b["env_state"].shape[1]), p("stacked_rewards", torch.float32, shape=(N, 15)),
-            p("reset_buf", torch.int64, shape=(N,)), p("progress_buf", torch.int64, shape=(N,)), p("total_mass", torch.float32, numel=N),
-            self.part.data_ptr(), self.ct.data_ptr())
-
-    def _stream(self):
-        import torch
-        return torch.cuda.current_stream(self.env._tdev).cuda_stream
+            N, self.bins, self.min_episode_step, int(self.skip_pushes), p("root_states", f, shape=(N, 13)), p("dof_state", f, numel=N * 66),
+            p("contact_forces", f, shape=(N, env.num_bodies, 3)), p("env_state", f, numel=N * env._buf["env_state"].shape[1]),
+            p("stacked_rewards", f, shape=(N, 15)), p("reset_buf", i64, shape=(N,)), p("progress_buf", i64, shape=(N,)),
+            p("total_mass", f, numel=N), self.part.data_ptr(), self.ct.data_ptr())
 
     def record(self):
         """After a step, on the step's stream (DyrosDynamicWalk.step calls it)."""
-        cbind.check(self.api, self.api["record"](*self._record_args, self._stream()))
+        self._launch("record", self._record_args)
 
     def reset_totals(self):
         """Starts a new window."""
-        cbind.check(self.api, self.api["clear"](self.num_envs, self.bins, self.part.data_ptr(), self.ct.data_ptr(), self._stream()))
+        self._launch("clear", (self.num_envs, self.bins, self.part.data_ptr(), self.ct.data_ptr()))
 
     def raw(self):
         """(table [bins, DWG_W] int64, counters [DWG_CT_WORDS] int64) as numpy arrays: one launch, one device-to-host copy."""
-        cbind.check(self.api, self.api["summarize"](self.num_envs, self.bins, self.part.data_ptr(), self.ct.data_ptr(), self.out.data_ptr(),
-                                                    self._stream()))
+        self._launch("summarize", (self.num_envs, self.bins, self.part.data_ptr(), self.ct.data_ptr(), self.out.data_ptr()))
         o = self.out.cpu().numpy()
         return o[:self.bins * W].reshape(self.bins, W).copy(), o[self.bins * W:].copy()
 

@@ -105,7 +105,7 @@ def joint_space_force(r, tau_joint=None, gen_force=None):
         r[:, 6:] += tau_joint
 
 
-class ModelTensor:
+class ModelTensor(cbind.Launcher):
     """The base of the features' classes: the entry points, the host's bound buffers as checked pointers, and the launch.  A subclass is its
     buffers, its argument tuples (built once: the host's buffers are bound once, so no argument changes from call to call) and its methods."""
 
@@ -148,11 +148,3 @@ class ModelTensor:
         if armature is None:
             return a
         return a + (self._in("mass_scale", shape=(N, NB)), self._in("dof_armature", shape=(N, K["DWJ_NUM_DOF"])) if armature else None)
-
-    def _stream(self) -> int:
-        import torch
-        return torch.cuda.current_stream(self._tdev).cuda_stream
-
-    def _launch(self, entry: str, args: tuple) -> None:
-        """One launch on torch's current stream."""
-        cbind.check(self.api, self.api[entry](*args, self._stream()))

@@ -32,9 +32,9 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, cbind
-from .cbind import check as _check
+from . import cbind
 from .ppo_update import _req
+from .recorders import Recorder
 
 K = cbind.constants("dyros_trace.h", "dwt_")
 EXPORTS = list(cbind.signatures("dyros_trace.h", "dwt_"))
@@ -162,17 +162,15 @@ def write_txt(directory: str, one: dict) -> list:
     return paths
 
 
-class RunTrace:
+class RunTrace(Recorder):
     """The trace of one DyrosDynamicWalk env (see the module docstring).  Buffers are allocated here, once."""
 
     CHANNELS = CHANNELS
 
     def __init__(self, env, spec: dict):
-        self.api = declare(_lib.load()[0])
-        self.env = env
-        N, dev = env.num_envs, env._tdev
+        super().__init__(env, declare)
+        N, dev = self.num_envs, self._tdev
         validate(spec, N)
-        self.num_envs = N
         self.depth = int(spec.get("depth", 512))
         self.hold = spec.get("hold", "fall")
         ids = resolve_env_ids(spec.get("env_ids", 64), N)
@@ -181,20 +179,14 @@ class RunTrace:
         self.ss = torch.zeros(K["DWT_SS_WORDS"], self.num_slots, dtype=torch.int32, device=dev)
         self.slot_env = torch.zeros(self.num_slots, dtype=torch.int32, device=dev)
         self.env_slot = torch.zeros(N, dtype=torch.int32, device=dev)
-        # dwt_record's arguments, checked once: no argument changes from call to call (the env's buffers are bound once, load_state_dict
-        # copies into them), so a step pays one ctypes call
-        b = env._buf
-        p = lambda name, dt, **kw: _req(name, b[name], dt, **kw).data_ptr()          # noqa: E731
+        p, f, i64 = self._in, torch.float32, torch.int64
         self._record_args = (
-            N, self.num_slots, self.depth, HOLD[self.hold], self.slot_env.data_ptr(), p("root_states", torch.float32, shape=(N, 13)),
-            p("dof_state", torch.float32, numel=N * 66), p("contact_forces", torch.float32, shape=(N, env.num_bodies, 3)),
-            p("env_state", torch.float32, numel=N * b["env_state"].shape[1]), p("rew_buf", torch.float32, numel=N),
-            p("stacked_rewards", torch.float32, shape=(N, 15)), p("reset_buf", torch.int64, shape=(N,)), p("timeout_buf", torch.int64, shape=(N,)),
-            float(env.max_episode_length), self.ss.data_ptr(), self.ring.data_ptr())
+            N, self.num_slots, self.depth, HOLD[self.hold], self.slot_env.data_ptr(), p("root_states", f, shape=(N, 13)),
+            p("dof_state", f, numel=N * 66), p("contact_forces", f, shape=(N, env.num_bodies, 3)),
+            p("env_state", f, numel=N * env._buf["env_state"].shape[1]), p("rew_buf", f, numel=N), p("stacked_rewards", f, shape=(N, 15)),
+            p("reset_buf", i64, shape=(N,)), p("timeout_buf", i64, shape=(N,)), float(env.max_episode_length), self.ss.data_ptr(),
+            self.ring.data_ptr())
         self.retarget(ids)
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.env._tdev).cuda_stream
 
     def retarget(self, env_ids):
         """Traces these envs (as many as before) from now on: every slot is cleared and armed."""
@@ -211,20 +203,19 @@ class RunTrace:
 
     def record(self):
         """After a step, on the step's stream (DyrosDynamicWalk.step calls it)."""
-        _check(self.api, self.api["record"](*self._record_args, self._stream()))
+        self._launch("record", self._record_args)
 
     def arm(self, env_ids: torch.Tensor = None):
         """Releases and clears the slots of env_ids (None: every slot); envs that are not traced, or out of range, are ignored."""
         N = self.num_envs
-        pb = _req("progress_buf", self.env._buf["progress_buf"], torch.int64, shape=(N,))
         ids, n = None, N
         if env_ids is not None:
             ids = _req("env_ids", torch.as_tensor(env_ids, device=self.ss.device).to(torch.int32), torch.int32)
             n = ids.numel()
             if n == 0:
                 return
-        _check(self.api, self.api["arm"](N, self.num_slots, ids.data_ptr() if ids is not None else None, n, pb.data_ptr(),
-                                         self.env_slot.data_ptr(), self.ss.data_ptr(), self._stream()))
+        self._launch("arm", (N, self.num_slots, ids.data_ptr() if ids is not None else None, n, self._in("progress_buf", torch.int64, shape=(N,)),
+                             self.env_slot.data_ptr(), self.ss.data_ptr()))
 
     def held(self) -> torch.Tensor:
         """Device bool [K], in slot order (self.env_ids); no sync."""
@@ -235,8 +226,8 @@ class RunTrace:
         n = ids.numel()
         out = torch.empty(n, self.depth, ROW_WORDS, dtype=torch.int32, device=self.ss.device)
         rows = torch.empty(n, dtype=torch.int32, device=self.ss.device)
-        _check(self.api, self.api["gather"](self.num_slots, self.depth, ids.data_ptr(), n, self.ss.data_ptr(), self.ring.data_ptr(),
-                                            out.data_ptr(), rows.data_ptr(), self._stream()))
+        self._launch("gather", (self.num_slots, self.depth, ids.data_ptr(), n, self.ss.data_ptr(), self.ring.data_ptr(), out.data_ptr(),
+                                rows.data_ptr()))
         st = self.ss[:, ids.long()].t().contiguous()
         flat_ = torch.cat([out.reshape(-1), rows, st.reshape(-1), ids]).cpu().numpy()
         w = n * self.depth * ROW_WORDS

@@ -76,7 +76,7 @@ def snapshot(env):
 
 
 # ---------------------------------------------------------------------------------------------- 1. synthetic buffers through the kernels
-@pytest.mark.parametrize("n", [1, 31, 33, 300])
+@pytest.mark.parametrize("n", [1, 31, 32, 33, 300])
 def test_kernels_match_numpy_on_synthetic_buffers(n):
     """dwe_record / dwe_summarize called directly at the group edges of a 32-env workgroup (the tail group partly empty): every cause bit and
     the rare combinations (FLY among them), adoption, outside resets, unreset envs, non-finite rows, a window restart and restarts."""

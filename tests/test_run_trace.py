@@ -334,10 +334,23 @@ def test_export_txt_and_npz_round_trip(host, tmp_path):
         assert np.array_equal(z["flag_" + flag], (z["flags"] & bit) != 0)
 
 
-def test_an_empty_spec_is_the_default_trace():
+def test_an_empty_spec_is_the_default_trace(monkeypatch):
+    import types
+    from isaacgymdyros_amd import gait_profile, recorders, run_trace
     from isaacgymdyros_amd.config import default_cfg, validate_cfg
     cfg = default_cfg(64, "cpu")
     cfg["sim"]["mi355"]["run_trace"] = {}          # 64 envs, 512 steps, hold "fall": on, as DyrosDynamicWalk reads it too
     validate_cfg(cfg)
-    src = open(os.path.join(ROOT, "isaacgymdyros_amd", "dyros_dynamic_walk.py")).read()
-    assert "spec is not None and spec is not False" in src
+    # what DyrosDynamicWalk attaches is recorders.attach's decision: {} and True switch a recorder on (with that spec), None and False off
+    monkeypatch.setattr(run_trace, "RunTrace", lambda env, spec: ("run_trace", spec))
+    monkeypatch.setattr(gait_profile, "GaitProfile", lambda env, spec: ("gait_profile", spec))
+    for key in ("run_trace", "gait_profile"):
+        for spec, on in (({}, True), (True, True), (None, False), (False, False)):
+            assert recorders.is_on(spec) is on
+            env = types.SimpleNamespace(extras={})
+            recorders.attach(env, {key: spec})
+            assert getattr(env, key) == ((key, spec) if on else None)
+            assert all(getattr(env, other) is None for other, _, _ in recorders.WALK if other != key)
+    env = types.SimpleNamespace(extras={})
+    recorders.attach(env, {})
+    assert all(getattr(env, name) is None for name, _, _ in recorders.WALK)

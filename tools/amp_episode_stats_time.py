@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of TocabiAMPLower's episode statistics: wall time per step() + reset_done() at 16384 envs with amp_fused and
+"""Cost of TocabiAMPLower's episode statistics: milliseconds per eager step() + reset_done() at 16384 envs with amp_fused and
 device draws, cfg sim.mi355.amp_episode_stats off and on in the same process, same seed and actions, each after a warm-up.  Run under
 `rocprofv3 --kernel-trace --stats -- python tools/amp_episode_stats_time.py --only-on` for dwe_k_record's own time.
 
@@ -11,43 +11,28 @@ import json
 import os
 import sys
 import tempfile
-import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from _timing import DEV, ROOT, actions, loop_ms, make_amp_env
+
 FUSED = {"amp_fused": True, "amp_hist_ring": True, "amp_device_draws": True}
 
 
 def make(n, mi, episode_length=None, motion=False):
-    from isaacgymdyros_amd.tocabi_amp_lower import TocabiAMPLower, default_amp_cfg
-    cfg = default_amp_cfg(n, "cuda:0")
-    cfg["sim"]["mi355"] = dict(mi)
-    if episode_length is not None:
-        cfg["env"]["episodeLength"] = episode_length
+    env = {} if episode_length is None else {"episodeLength": episode_length}
     if motion:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import amp_motion_synth as SY
-        cfg["env"].update({"stateInit": "Random", "motion_file": SY.write(tempfile.mkdtemp(prefix="amp_synth_"))})
-    return TocabiAMPLower(cfg, "cuda:0", 0, True)
+        env.update({"stateInit": "Random", "motion_file": SY.write(tempfile.mkdtemp(prefix="amp_synth_"))})
+    return make_amp_env(n, mi, env)
 
 
 def run(n, steps, warmup, on):
     env = make(n, dict(FUSED, amp_episode_stats=on))
-    g = torch.Generator(device="cuda:0").manual_seed(0)
-    acts = [(torch.rand(n, 12, generator=g, device="cuda:0") * 2 - 1) * 0.5 for _ in range(8)]
-    for t in range(warmup):
-        env.reset_done()
-        env.step(acts[t % 8])
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for t in range(steps):
-        env.reset_done()
-        env.step(acts[t % 8])
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) / steps * 1e3
-    out = {"amp_episode_stats": on, "num_envs": n, "ms_per_step_and_reset_done": ms}
+    a = actions(n, 12, 0.5)
+    out = {"amp_episode_stats": on, "num_envs": n,
+           "ms_per_step_and_reset_done": loop_ms(lambda t: (env.reset_done(), env.step(a[t % 8])), steps, warmup)}
     if on:
         s = env.episode_stats.summary()
         out["episodes"], out["causes"], out["mean_length"] = s["episodes"], s["causes"], s["mean_length"]
@@ -58,12 +43,12 @@ def run(n, steps, warmup, on):
 def lengths(n, steps):
     for name, mi, motion in (("torch", {}, False), ("fused", FUSED, False), ("motion", dict(FUSED, amp_motion_device=True), True)):
         env = make(n, dict(mi, amp_episode_stats=True), episode_length=100000, motion=motion)
-        g = torch.Generator(device="cuda:0").manual_seed(0)
-        amp = torch.linspace(0.0, 1.0, n, device="cuda:0").unsqueeze(1)
+        g = torch.Generator(device=DEV).manual_seed(0)
+        amp = torch.linspace(0.0, 1.0, n, device=DEV).unsqueeze(1)
         ended = []
         for _ in range(steps):
             env.reset_done()
-            _o, _r, reset, _x = env.step((torch.rand(n, 12, generator=g, device="cuda:0") * 2 - 1) * amp)
+            _o, _r, reset, _x = env.step((torch.rand(n, 12, generator=g, device=DEV) * 2 - 1) * amp)
             ended.append(env.progress_buf[reset.view(-1) != 0].cpu())
         ln = torch.cat(ended).float()
         s = env.episode_stats.summary()

@@ -9,16 +9,13 @@ import argparse
 import importlib.util
 import json
 import os
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-DEV = "cuda:0"
+from _timing import DEV, ROOT, chain_us
 
 
-def kernel(n, cols, launches, warmup):
+def kernel(n, cols, launches):
     from isaacgymdyros_amd.game_meter import GameMeter
     g = torch.Generator(device=DEV).manual_seed(0)
     m = GameMeter(n, DEV, cols=cols, games_to_track=100)
@@ -26,25 +23,7 @@ def kernel(n, cols, launches, warmup):
     stacked = torch.randn(n, 15, generator=g, device=DEV)
     done = (torch.rand(n, generator=g, device=DEV) < 1.0 / 500).to(torch.int64)
     args = (rew, done, stacked if cols > 1 else None)
-    for _ in range(warmup):
-        m.record(*args)
-    torch.cuda.synchronize()
-    chain = 100
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    gr = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(gr, stream=side):
-        for _ in range(chain):
-            m.record(*args)
-    gr.replay()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(launches // chain):
-        gr.replay()
-    e1.record()
-    torch.cuda.synchronize()
-    us = e0.elapsed_time(e1) / (launches // chain * chain) * 1e3
+    us = chain_us(lambda: m.record(*args), launches)
     # bytes: every column of cur read and written, the increments and the flags read
     moved = n * (8 * (cols + 1) + 4 * cols + 8)
     s = m.summary()
@@ -75,7 +54,7 @@ def main():
         print(json.dumps(consumer(a.num_envs, a.epochs, True)), flush=True)
         return
     for cols in (1, 16):
-        print(json.dumps(kernel(a.num_envs, cols, 2000, 200)), flush=True)
+        print(json.dumps(kernel(a.num_envs, cols, 2000)), flush=True)
     for _ in range(a.rounds):
         for on in (False, True):
             print(json.dumps(consumer(a.num_envs, a.epochs, on)), flush=True)

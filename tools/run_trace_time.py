@@ -1,46 +1,19 @@
 #!/usr/bin/env python3
 """Cost of the run trace at --num-envs envs: microseconds per dwt_k_record alone (device events around replays of a
 captured chain of 100 launches on the buffers a step left, so that the host's launch rate does not bound it) for K = 64 and K = all envs, and
-wall time per eager step() with cfg sim.mi355.run_trace off and on, same seed and actions, each after a warm-up.  The timed traces never hold:
+milliseconds per eager step() with cfg sim.mi355.run_trace off and on, same seed and actions, each after a warm-up.  The timed traces never hold:
 a held slot only counts, and with hold "fall" every slot is held after a few hundred steps of random actions.  Run under
 `rocprofv3 --kernel-trace --stats -- python tools/run_trace_time.py --only-on [--slots K]` for the kernel's own time within a step."""
 import argparse
 import json
-import os
-import sys
-import time
 
-import torch
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-
-def make(n, trace):
-    from isaacgymdyros_amd.config import default_cfg
-    from isaacgymdyros_amd.dyros_dynamic_walk import DyrosDynamicWalk
-    cfg = default_cfg(n, "cuda:0")
-    cfg["sim"]["mi355"]["alias_obs"] = True
-    if trace:
-        cfg["sim"]["mi355"]["run_trace"] = trace
-    return DyrosDynamicWalk(cfg, "cuda:0", 0, True)
-
-
-def acts(n):
-    g = torch.Generator(device="cuda:0").manual_seed(0)
-    return [torch.rand(n, 13, generator=g, device="cuda:0") * 2 - 1 for _ in range(8)]
+from _timing import actions, chain_us, loop_ms, make_env
 
 
 def run(n, steps, warmup, trace):
-    env = make(n, trace)
-    a = acts(n)
-    for t in range(warmup):
-        env.step(a[t % 8])
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for t in range(steps):
-        env.step(a[t % 8])
-    torch.cuda.synchronize()
-    out = {"run_trace": trace or None, "num_envs": n, "ms_per_step": (time.perf_counter() - t0) / steps * 1e3}
+    env = make_env(n, "run_trace", trace, alias_obs=True)
+    a = actions(n)
+    out = {"run_trace": trace or None, "num_envs": n, "ms_per_step": loop_ms(lambda t: env.step(a[t % 8]), steps, warmup)}
     if trace:
         r = env.run_trace
         out["held"], out["ring_MB"] = int(r.held().sum()), r.ring.numel() * 4 / 1e6
@@ -48,33 +21,13 @@ def run(n, steps, warmup, trace):
     return out
 
 
-def kernel(n, k, depth, launches, warmup):
+def kernel(n, k, depth, launches):
     """dwt_k_record alone on the buffers a few steps left; hold never, so every launch writes K rows."""
     from isaacgymdyros_amd.run_trace import ROW_BYTES
-    env = make(n, {"env_ids": k, "depth": depth, "hold": "never"})
-    a = acts(n)
-    for t in range(8):
-        env.step(a[t])
-    r = env.run_trace
-    for _ in range(warmup):
-        r.record()
-    torch.cuda.synchronize()
-    chain = 100
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        for _ in range(chain):
-            r.record()
-    g.replay()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(launches // chain):
-        g.replay()
-    e1.record()
-    torch.cuda.synchronize()
-    us = e0.elapsed_time(e1) / (launches // chain * chain) * 1e3
+    env = make_env(n, "run_trace", {"env_ids": k, "depth": depth, "hold": "never"}, alias_obs=True)
+    for a in actions(n):
+        env.step(a)
+    us = chain_us(env.run_trace.record, launches)
     # bytes per slot: the row out, and in the 13 + 66 + 114 + 16 words the row comes from, the env_state spans (33 + 37 + 13 + 12 + 2 + 1 + 3
     # words) and the two flags
     moved = k * (ROW_BYTES + 4 * (13 + 66 + 114 + 16 + 101) + 16)
@@ -98,7 +51,7 @@ def main():
         print(json.dumps(run(n, a.steps, a.warmup, {"env_ids": min(a.slots, n), "depth": a.depth, "hold": "never"})), flush=True)
         return
     for k in (min(64, n), n):
-        print(json.dumps(kernel(n, k, a.depth, 2000, 200)), flush=True)
+        print(json.dumps(kernel(n, k, a.depth, 2000)), flush=True)
     for trace in (None, small, full, None, small, full):
         print(json.dumps(run(n, a.steps, a.warmup, trace)), flush=True)
 
